@@ -8,9 +8,16 @@ written to a rotating HBM buffer). The timed region starts with every complex's 
 (node [N,113], edge [E,28], ids) resident in HBM and ends with the outputs in HBM.
 
 Multi-GPU (torchrun): complexes are sharded, each rank owns its 1024; no collective in the timed
-region (weak scaling); value = total complexes / max-over-ranks time. After the timed region the
-C4 driver (distributed.predict_sharded) runs on real complexes and the contact-map all-gather is
-timed at the metric's size (supplementary record).
+region (weak scaling); value = total complexes / max-over-ranks time.
+
+A plain run does only what the headline needs: it builds the inputs, warms up, times --steps steps,
+writes the last step's outputs if --dump-outputs DIR is given, and prints the result line. --full adds
+every supplementary record (each can still be switched off by its own --no-* option): the per-kernel
+table and roofline of the GeoT kernels (one extra step bracketed by HIP events), the host issue cost
+(one extra step), the warm graph-builder timing (a second builder call), the fused head prologue, the
+fp32 and general-path sub-records, the CPU baseline, and -- in a process group (torchrun, or --dist)
+-- the C4 driver (distributed.predict_sharded) on real complexes with the contact-map all-gather
+timed at the metric's size.
 
 Prints ONE JSON line on rank 0.
 """
@@ -339,14 +346,17 @@ class SerialSchedule:
         pass
 
 
-def timed(sch, steps, warmup, ws=1, kernel_events="dominant"):
+def timed(sch, steps, warmup, ws=1, kernel_events="dominant", full=True):
     """(elapsed seconds of `steps` steps, bracketed by barrier + synchronize, max over ranks;
     per-kernel HIP event pairs). The overlapped schedule's drain (finish) is inside the timed region.
 
     kernel_events "dominant" (default): inside the timed region only the pair-tensor launches are
     bracketed by HIP events (the overlapped schedule: ONE pair-stream launch per step), so the dominant
     kernel's roofline is measured live; the GeoT kernels' event pairs come from one untimed step after
-    it. "all": every launch in the timed region is bracketed."""
+    it. "all": every launch in the timed region is bracketed.
+
+    full=False (a plain bench run) issues nothing after the timed region: no GeoT kernel events with
+    "dominant", and no idle-issue measurement (host_issue_idle_s is None)."""
     for _ in range(warmup):
         sch.step()
     sch.finish()
@@ -365,21 +375,24 @@ def timed(sch, steps, warmup, ws=1, kernel_events="dominant"):
     barrier(ws)
     elapsed = max_over_ranks(ws, time.perf_counter() - t0)
     c1 = sch.check() if hasattr(sch, "check") else None
-    if kernel_events != "all":
+    if full and kernel_events != "all":
         sch.step(None, events)
         sch.finish()
         torch.cuda.synchronize()
     # pure host cost of issuing one step, apart from back-pressure: the same step issued onto idle
     # streams (drained first), timed to the end of its issue
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    sch.step()
-    host_issue_idle_s = time.perf_counter() - t1
-    sch.finish()
-    torch.cuda.synchronize()
+    host_issue_idle_s = None
+    if full:
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        sch.step()
+        host_issue_idle_s = time.perf_counter() - t1
+        sch.finish()
+        torch.cuda.synchronize()
     queue = None
     if c0 is not None:
-        sch.check()
+        if full:
+            sch.check()
         queue = {"stream_bytes": c1["stream_bytes"] - c0["stream_bytes"], "help_bytes": c1["help_bytes"] - c0["help_bytes"],
                  "gave_up": c1["gave_up"] - c0["gave_up"]}
     return elapsed, events, {"host_issue_s": host_issue_s, "host_issue_idle_s": host_issue_idle_s, "queue": queue,
@@ -412,6 +425,8 @@ def roofline_of(kern, dtype, traffic=None, mfma_only=False):
     rate beside it."""
     # kernels with a rate only (a pair-stream launch the help launches left no bytes to has none)
     cands = {n: r for n, r in kern.items() if ("tflops" in r if mfma_only else ("tflops" in r or "gbs" in r))}
+    if not cands:
+        return None
     dom = max(cands, key=lambda n: cands[n]["total_ms"])
     d = kern[dom]
     if "tflops" in d:
@@ -469,6 +484,46 @@ def finish_kernel_table(kern, pair_bytes):
     return kern
 
 
+DUMP_ARRAY_BYTES = 12 << 20  # per array as float32: four arrays stay well under 64 MB in all
+
+
+def last_step_outputs(sch, eng, gb_last, layers):
+    """What the timed schedule's last micro-batch left in HBM, by name: the arrays a caller of
+    GeoTEngine.forward(clone=False) + the pair-tensor op receives. Read after the schedule has drained
+    and the device is synchronised, before anything else runs on the engine.
+
+    node_feats [Nt, 128], edge_feats [Et, 128]: the forward's return values, i.e. the workspace buffers
+    the last layer wrote (the engine's h / f double buffers alternate once per layer);
+    node_feats_T [128, Nt]: engine.last_hT, the pair tensor's input; pair_tensor: the flat buffer
+    holding the micro-batch's [256, L1, L2] pair tensors back to back. The overlapped bench schedule
+    rotates two sinks that several jobs in flight may write at once (discard_outputs); every job that
+    shares a sink computes the same values when micro_batch * 2 is a multiple of --pool (the default
+    shapes: 8 * 2 = 16), so the sink's content does not depend on their order."""
+    ws = eng.workspace(gb_last.num_nodes, gb_last.num_edges)
+    if hasattr(sch, "sinks"):
+        pair = sch.sinks[(sch.next_job - 1) % len(sch.sinks)][:sch.numel]
+    else:
+        pair = sch.pair_buf
+    return {"node_feats": ws["h"][layers % 2], "edge_feats": ws["f"][(layers - 1) % 2],
+            "node_feats_T": eng.last_hT, "pair_tensor": pair}
+
+
+def dump_outputs(path, arrays, limit=DUMP_ARRAY_BYTES):
+    """Write each tensor as <path>/<name>.npy in float32 (bf16 -> fp32 is exact): whole if it fits
+    `limit` bytes, else the elements at a fixed, seeded set of flat indices (sorted; the same indices
+    for the same shape in every run and build)."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        keep = limit // 4
+        if flat.numel() <= keep:
+            a = flat.float().cpu().numpy().reshape(tuple(t.shape))
+        else:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), keep))
+            a = flat[torch.as_tensor(idx, device=flat.device)].float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def sub_record(what, dtype, geo_ref, complexes, pool_gb, P, M, n_res, k, args, dev, sd, cfg, s_geot, s_pair,
                steps=3, warmup=1):
     """Supplementary C3 line outside the metric: the same schedule on `complexes` complexes in
@@ -508,11 +563,19 @@ def sub_record(what, dtype, geo_ref, complexes, pool_gb, P, M, n_res, k, args, d
     return out
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the supplementary records (GeoT per-kernel table and roofline, host issue "
+                         "cost, warm builder call, head prologue, fp32 / general-path sub-records, CPU baseline, "
+                         "and the contact-map all-gather in a process group); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step's last micro-batch computed as "
+                         "DIR/<name>.npy (float32; large arrays as a fixed seeded sample): node_feats, "
+                         "edge_feats, node_feats_T, pair_tensor")
     ap.add_argument("--complexes", type=int, default=1024, help="complexes per GPU per step")
     ap.add_argument("--micro-batch", type=int, default=8)
     ap.add_argument("--residues", type=int, default=1000)
@@ -520,10 +583,10 @@ def main():
     ap.add_argument("--pool", type=int, default=16, help="distinct synthetic complexes replicated in HBM")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--cpu-sample", type=int, default=20)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-prologue", action="store_true", help="skip the supplementary fused-head-prologue line")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-prologue", action="store_true", help="--full: skip the supplementary fused-head-prologue line")
     ap.add_argument("--no-sub", action="store_true",
-                    help="skip the supplementary fp32 and general-path (geo_ref off) C3 sub-records")
+                    help="--full: skip the supplementary fp32 and general-path (geo_ref off) C3 sub-records")
     ap.add_argument("--overlap", type=int, default=1, choices=[0, 1],
                     help="1: GeoT on one stream, the pair tensors on the device-queue pair stream beside it "
                          "(deepinteract_amd.pipeline); 0: both on one stream, one after the other")
@@ -558,11 +621,11 @@ def main():
     ap.add_argument("--geo-ref", type=int, default=1, choices=[0, 1],
                     help="0: clear DI_GRAPH_GEO_REF on every batch (the general path; diagnostic)")
     ap.add_argument("--dist", action="store_true",
-                    help="create the RCCL process group even at world size 1 (runs the contact-map "
-                         "all-gather record on one GPU)")
+                    help="create the RCCL process group even at world size 1 (with --full: runs the "
+                         "contact-map all-gather record on one GPU)")
     ap.add_argument("--lib", default=None, help="a variant build of the HIP library (deepinteract_amd.build."
                                                  "build_variant; tests and diagnostics)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.lib:
         from deepinteract_amd import _lib
         _lib.load_variant(args.lib)
@@ -620,9 +683,9 @@ def main():
     t_synth = time.perf_counter() - tb
     # the whole pool in one builder call (one launch per stage); neighbour ids as the reference
     # draws them after torch.manual_seed(s) per chain (bit-exact mode). Timed twice: the first
-    # (cold) call also pays module loading and the pinned staging allocation.
+    # (cold) call also pays module loading and the pinned staging allocation. A plain run builds once.
     t_builds = []
-    for _ in range(2):
+    for _ in range(2 if args.full else 1):
         torch.cuda.synchronize()
         tb = time.perf_counter()
         pool_gb = build_graph_batch([ch for pair_ in pool for ch in pair_], k=k, device=dev,
@@ -630,7 +693,7 @@ def main():
                                     nbr_seeds=[2 * (1000 * rank + c) + s + 1 for c in range(P) for s in (0, 1)])
         torch.cuda.synchronize()
         t_builds.append(time.perf_counter() - tb)
-    t_build = t_builds[1]
+    t_build = t_builds[-1]
     # resident batch: complexes -> micro-batches (copies of pool complexes, distinct HBM buffers)
     n_mb = args.complexes // M
     mbs = [select_graphs(pool_gb, [2 * ((m * M + j) % P) + s for j in range(M) for s in (0, 1)])
@@ -653,12 +716,16 @@ def main():
     else:
         s_geot = s_pair = torch.cuda.current_stream(dev)
     sch = make_schedule(args, eng, mbs, h1r, h2r, l1, l2, tdt, dev, s_geot, s_pair)
-    elapsed, events, info = timed(sch, args.steps, args.warmup, ws, args.kernel_events)
+    elapsed, events, info = timed(sch, args.steps, args.warmup, ws, args.kernel_events, args.full)
     total = args.complexes * args.steps * ws
     value = total / elapsed
+    if args.dump_outputs and rank == 0:
+        # first after the timed region (a plain run issued nothing since; --full's extra steps repeat
+        # the same step on the same inputs)
+        dump_outputs(args.dump_outputs, last_step_outputs(sch, eng, mbs[-1], args.layers))
 
     # ---- supplementary (outside the metric) ------------------------------------------------
-    prologue = head_prologue_record(h1r, h2r, l1, l2, mbs[-1], eng, dev, tdt) if not args.no_prologue else None
+    prologue = head_prologue_record(h1r, h2r, l1, l2, mbs[-1], eng, dev, tdt) if args.full and not args.no_prologue else None
     nodes, edges, geo_ref0 = gb0.num_nodes, gb0.num_edges, gb0.geo_ref
     l1l2 = sum(2 * H * a * b * esz for a, b in zip(l1, l2))
     kern = kernel_table(events, nodes, edges, l1l2, esz, args.dtype, geo_ref0)
@@ -668,19 +735,21 @@ def main():
     del sch, mbs, gb0, eng, events
     gc.collect()
     torch.cuda.empty_cache()
-    gather = allgather_record(ws, rank, args.complexes, n_res, k, dev) if dist_on() and args.config == "c3" else None
+    gather = allgather_record(ws, rank, args.complexes, n_res, k, dev) \
+        if args.full and dist_on() and args.config == "c3" else None
     # the committed PMC summary was collected on the default workload (C3, micro-batch 8, bf16, the
     # default schedule): any other shape reports traffic null rather than borrowing those bytes
     pmc_shape = (args.config, M, n_res, k, args.layers, args.dtype, args.overlap, args.geo_ref) == \
         ("c3", 8, 1000, 20, 2, "bf16", 1, 1)
     roof = roofline_of(kern, args.dtype)
-    if args.overlap and roof["kernel"] == "pair_tensor" and info["mode"] == "overlapped":
+    if roof is not None and args.overlap and roof["kernel"] == "pair_tensor" and info["mode"] == "overlapped":
         # one persistent launch spans the step: its duration includes the waves' waits for each job's
         # signal, so this is the stream's rate over the step, a lower bound on its store bandwidth
         # (the standalone rate of the same launch shape: tools/diag/pair_alone.py)
         roof["achieved_is"] = "bytes the pair-stream launch stored / its whole duration (waits for signals included)"
-    roof["traffic"] = load_pmc_traffic(roof["kernel"], kern.get(roof["kernel"], {}).get("bytes_per_launch")) \
-        if pmc_shape else None
+    if roof is not None:
+        roof["traffic"] = load_pmc_traffic(roof["kernel"], kern.get(roof["kernel"], {}).get("bytes_per_launch")) \
+            if pmc_shape else None
     bytes_c = algorithmic_bytes_per_complex(n_res, n_res, k, esz)
     hbm_frac = bytes_c * value / ws / (HBM_PEAK_GBS * 1e9)
     flops_c = algorithmic_flops_per_complex(n_res, n_res, k, args.layers)
@@ -723,11 +792,12 @@ def main():
                    + ("; node embedding as the first blocks of the InitEdge launch"
                       if args.init_kernel == "fused" and args.geo_ref else "")
                    + ("; HIP events around every launch in the timed region" if args.kernel_events == "all" else
-                      "; HIP events around the pair-tensor launches only (GeoT kernel events from an untimed step)")
+                      "; HIP events around the pair-tensor launches only (GeoT kernel events from an untimed step)"
+                      if args.full else "; HIP events around the pair-tensor launches only")
                    + f"; edge-layer kernel {EDGE_KERNEL[args.dtype]}"},
         # pure host cost of issuing one step (every launch of the step issued onto drained streams, to
         # the end of its issue): the GPU cannot wait for the host while this stays well below ms_per_step
-        "host_issue_ms_per_step": round(info["host_issue_idle_s"] * 1e3, 3),
+        "host_issue_ms_per_step": round(info["host_issue_idle_s"] * 1e3, 3) if args.full else None,
         # the timed loop's issue time per step; it includes waiting for room in the HIP queues
         # (back-pressure from the GPU), so on a long run it approaches ms_per_step by construction
         "host_issue_timed_region_ms_per_step": round(info["host_issue_s"] / args.steps * 1e3, 3),
@@ -737,10 +807,12 @@ def main():
         "algorithmic_per_complex": {"bytes": bytes_c, "flops": flops_c, "executed_mfma_flops": xflops_c,
                                     "mfma_peak_tflops": MFMA_PEAK_TFLOPS[args.dtype], "hbm_peak_gbs": HBM_PEAK_GBS},
         "roofline": roof,
-        "roofline_geot": roofline_of(kern, args.dtype, mfma_only=True) if any("tflops" in r for r in kern.values()) else None,
+        "roofline_geot": roofline_of(kern, args.dtype, mfma_only=True),
         "pair_queue": queue,
         "kernels": rounded(kern),
-        "builder": {"complexes": P, "build_s": round(t_build, 4), "ms_per_complex": round(t_build / P * 1e3, 3),
+        # build_s: the warm (second) builder call, measured with --full only
+        "builder": {"complexes": P, "build_s": round(t_build, 4) if args.full else None,
+                    "ms_per_complex": round(t_build / P * 1e3, 3) if args.full else None,
                     "cold_build_s": round(t_builds[0], 4),
                     "synth_host_s": round(t_synth, 3),
                     "what": "one builder call for the pool: kNN, features, topology, torch-seeded neighbour ids"},
@@ -749,7 +821,7 @@ def main():
         out["head_prologue"] = prologue
     if gather is not None:
         out["contact_map_allgather"] = gather
-    if not args.no_sub and args.config == "c3":
+    if args.full and not args.no_sub and args.config == "c3":
         # supplementary C3 lines outside the metric (same schedule and kernels): the reference's
         # precision (fp32, deepinteract_utils.py:1088) and the general path with the neighbour-edge
         # gathers live (DI_GRAPH_GEO_REF cleared, deepinteract_modules.py:384-418); the timed
@@ -760,7 +832,7 @@ def main():
             sub_record("bf16 C3, general path (DI_GRAPH_GEO_REF cleared: neighbour gathers live)", "bf16", False,
                        256, pool_gb, P, M, n_res, k, args, dev, sd, cfg, s_geot, s_pair),
         ]
-    if rank == 0 and ws == 1 and not args.no_cpu:
+    if args.full and rank == 0 and ws == 1 and not args.no_cpu:
         # the headline at the threads this job is given on the box (OMP_NUM_THREADS: its CPU share),
         # the protocol's one-thread-per-physical-core figure beside it (on a shared host the op-by-op
         # DGL-style path loses to oversubscription there: 0.32 vs 1.19 complexes/s in round 2)
@@ -784,6 +856,7 @@ def main():
     if dist_on():
         import torch.distributed as dist
         dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":

@@ -40,3 +40,23 @@ def test_pair_traffic_scales_to_the_launch():
     assert 1.0 <= rec["hbm_bytes_per_alg_byte"] < 1.1
     assert bench.load_pmc_traffic("pair_tensor") is None
     assert bench.load_pmc_traffic("edge_layer") > 0
+
+
+def test_dump_sample_of_a_large_array_is_fixed(tmp_path):
+    """--dump-outputs: above the per-array limit the file holds the elements at a seeded set of flat
+    indices -- the same indices in every call, sorted, within the limit; smaller arrays are whole."""
+    import numpy as np
+    import torch
+
+    import bench
+    t = torch.arange(5000, dtype=torch.float32).reshape(50, 100)
+    d = str(tmp_path)
+    bench.dump_outputs(d, {"x": t, "small": t[:2].bfloat16()}, limit=4000)
+    x1 = np.load(os.path.join(d, "x.npy"))
+    bench.dump_outputs(d, {"x": t.clone()}, limit=4000)
+    x2 = np.load(os.path.join(d, "x.npy"))
+    small = np.load(os.path.join(d, "small.npy"))
+    assert x1.shape == (1000,) and x1.dtype == np.float32 and np.array_equal(x1, x2)
+    assert (np.diff(x1) >= 0).all() and x1.min() >= 0 and x1.max() < 5000 and len(np.unique(x1)) > 500
+    assert small.shape == (2, 100) and small.dtype == np.float32
+    assert np.array_equal(small, t[:2].bfloat16().float().numpy())

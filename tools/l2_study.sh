@@ -3,7 +3,7 @@
 # requests (64-B vs whole) per kernel, each counter pair in its own --pmc pass (<= 4 TCC counters)
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$R"; export TMPDIR=/tmp; O="$R/gpurun_out"; mkdir -p "$O"
-P="--steps 1 --warmup 1 --no-cpu --no-sub --no-prologue --complexes 64"
+P="--full --steps 1 --warmup 1 --no-cpu --no-sub --no-prologue --complexes 64"
 specs=("list:60:cd /tmp && rocprofv3 -L > $O/counters_list.txt 2>&1")
 for sch in ov ser; do
   X=""; [ "$sch" = ser ] && X="--overlap 0"

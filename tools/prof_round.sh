@@ -5,9 +5,9 @@
 # tools/pmc_summary.py <tag> and copy the bench lines into profiles/.
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$R"; export TMPDIR=/tmp; O="$R/gpurun_out"; mkdir -p "$O"
-S="--steps 2 --warmup 1 --no-cpu --no-sub --complexes 256"
-P="--steps 1 --warmup 1 --no-cpu --no-sub --complexes 64"
-F="--dtype f32 --no-prologue --steps 2 --warmup 1 --no-cpu --no-sub --complexes 128"
+S="--full --steps 2 --warmup 1 --no-cpu --no-sub --complexes 256"
+P="--full --steps 1 --warmup 1 --no-cpu --no-sub --complexes 64"
+F="--full --dtype f32 --no-prologue --steps 2 --warmup 1 --no-cpu --no-sub --complexes 128"
 # usage: tools/prof_round.sh [a|b]   (a: tests + bench lines, b: profiles; default both: one call may
 # not hold both within gpurun's limit)
 PH="${1:-ab}"
@@ -15,10 +15,10 @@ if [[ "$PH" == *a* ]]; then
 "$R/tools/gpu_run.sh" \
   "pytest_gpu:600:python -u -m pytest tests -m gpu -q -rf --timeout 300 --timeout-method thread -p no:cacheprovider" \
   "smoke:200:python __graft_entry__.py smoke" \
-  "bench:400:python bench.py --steps 20 --warmup 5 > $O/bench.json" \
-  "bench_serial:300:python bench.py --overlap 0 --no-cpu > $O/bench_serial.json" \
-  "bench_dist:300:python bench.py --dist --no-cpu --no-sub --no-prologue --complexes 256 --steps 2 --warmup 1 > $O/bench_dist.json" \
-  "bench_c5:400:python bench.py --config c5 --steps 3 --warmup 1 > $O/bench_c5.json" \
+  "bench:400:python bench.py --full --steps 20 --warmup 5 > $O/bench.json" \
+  "bench_serial:300:python bench.py --full --overlap 0 --no-cpu > $O/bench_serial.json" \
+  "bench_dist:300:python bench.py --full --dist --no-cpu --no-sub --no-prologue --complexes 256 --steps 2 --warmup 1 > $O/bench_dist.json" \
+  "bench_c5:400:python bench.py --full --config c5 --steps 3 --warmup 1 > $O/bench_c5.json" \
   || exit $?
 fi
 if [[ "$PH" == *b* ]]; then

@@ -16,6 +16,10 @@ reusable runners are `tools/ab.sh` (interleaved A/B of bench configurations) and
 `tools/prof_round.sh` (end-of-round suite, bench lines and rocprofv3 passes). Regenerate this file
 with `python tools/session_index.py`.
 
+These scripts are command records and are kept as they ran: they predate `bench.py --full`, when every
+bench run also measured the supplementary records (per-kernel table, sub-records, CPU baseline). To
+repeat one, add `--full` to its `bench.py` commands; the reusable runners already pass it.
+
 | script | what it measured (its header) |
 |---|---|
 """
