@@ -67,6 +67,9 @@ struct EdgeArgs {
   float* attn_out = nullptr;
   float* attn_parts = nullptr;
   const int* in_ptr = nullptr;
+  // di_edge_layer_z (bf16 layer 0): f_in holds z0 rows; the InitEdge blob whose combined_linear_2
+  // blocks rebuild F0 from them
+  const void* init_wmat = nullptr;
 };
 
 struct NodeArgs {
@@ -383,9 +386,12 @@ struct InitX32Geo {
 // one 32-row tile of InitEdge; wt(phase) returns the phase's weight blocks (LDS) and gate_off(t) the
 // block offset of gate t (0 em, 1 dist, 2 dir, 3 orient, 4 amide) inside the gates phase.
 // acc enters holding emb[src] + emb[dst] slots (+ the orientation constant for GC).
+// init_tile_x32_z stops at zop, combined_linear_1's 32-wide output as a packed operand, and returns
+// the last phase's weights (combined_linear_1 at 0, combined_linear_2 at 8 blocks); init_tile_x32
+// goes on to f = combined_linear_2(zop).
 template <bool GC, class WT, class GO>
-__device__ __forceinline__ void init_tile_x32(X32<4>& acc, const P32<2>& gop, const float* wvec, int lane, int h,
-                                              WT&& wt, GO&& gate_off, X32<4>& f) {
+__device__ __forceinline__ const u16* init_tile_x32_z(X32<4>& acc, const P32<2>& gop, const float* wvec, int lane,
+                                                      int h, WT&& wt, GO&& gate_off, P32<2>& zop) {
   mma32<4, 2>(acc, gop, wt(0), lane);  // t = 0: the collapsed [128, 2] edge-message map
   constexpr int NT = GC ? 2 : 4;
 #pragma unroll 1
@@ -435,19 +441,24 @@ __device__ __forceinline__ void init_tile_x32(X32<4>& acc, const P32<2>& gop, co
       asm volatile("" : "+v"(acc.v[b]));  // computed here (not sunk past the next stage barrier)
     }
   }
-  // combined_linear_2(combined_linear_1(.)) : 128 -> 28 (padded 32) -> 128
-  {
-    const u16* w = wt(2 + NT);
-    P32<8> aop;
-    make_op32(aop, acc);
-    X32<1> z;
-    zero(z);
-    mma32<1, 8>(z, aop, w, lane);
-    P32<2> zop;
-    make_op32(zop, z);
-    zero(f);
-    mma32<4, 2>(f, zop, w + 8 * BLK, lane);
-  }
+  // combined_linear_1 : 128 -> 28 (padded 32)
+  const u16* w = wt(2 + NT);
+  P32<8> aop;
+  make_op32(aop, acc);
+  X32<1> z;
+  zero(z);
+  mma32<1, 8>(z, aop, w, lane);
+  make_op32(zop, z);
+  return w;
+}
+template <bool GC, class WT, class GO>
+__device__ __forceinline__ void init_tile_x32(X32<4>& acc, const P32<2>& gop, const float* wvec, int lane, int h,
+                                              WT&& wt, GO&& gate_off, X32<4>& f) {
+  P32<2> zop;
+  const u16* w = init_tile_x32_z<GC>(acc, gop, wvec, lane, h, wt, gate_off, zop);
+  // combined_linear_2 : 32 -> 128
+  zero(f);
+  mma32<4, 2>(f, zop, w + 8 * BLK, lane);
 }
 
 // acc = pos_src[node_pos[src]] + pos_dst[node_pos[dst]] (the orientation constant of GEO_REF batches
@@ -484,10 +495,14 @@ __device__ __forceinline__ void geo_op32(P32<2>& gop, const float* edge_f, int e
 // registers, leaving exactly one 32-register pair-tensor wave room beside them. At 161 (168 allocated)
 // the pair kernel's persistent blocks found no SIMD with room while InitEdge ran and the overlapped
 // pair tensor slowed from ~1050 to ~1540 us per micro-batch (round 4)
-template <bool GC>
+// Z (GC, no Fn): the tile stops at combined_linear_1's output and stores it as the 64-B z0 row
+// (mfma32.h) in a.f_out's place; combined_linear_2 is applied by layer 0's edge kernel
+// (k_edge_x32_ring<0, true, true>), so the 256-B F0 row is never written
+template <bool GC, bool Z = false>
 __global__ __attribute__((amdgpu_flat_work_group_size(1, InitX32Geo::THREADS), amdgpu_waves_per_eu(3, 3),
                           amdgpu_num_vgpr(80)))
 void k_init_x32(InitArgs a, EmbedArgs ea, int embed_blocks) {
+  static_assert(GC || !Z, "the z0 form is the DI_GRAPH_GEO_REF path");
   pq_signal_at_start(ea.sig_q, ea.sig_job);
   using G = InitGeo<BF16T>;
   constexpr int NW = InitX32Geo::NW;
@@ -519,10 +534,16 @@ void k_init_x32(InitArgs a, EmbedArgs ea, int embed_blocks) {
     if (p == 0) pipe.issue(W + (IE_T0 + 40 * geo_t(0)) * BLK, 40);
     else if (p < NT) pipe.issue(W + (IE_T0 + 40 * geo_t(p)) * BLK, 40);
     else if (p == NT) pipe.issue(W + IE_GEO1 * BLK, 40);
-    else if (p == NT + 1) pipe.issue(W + IE_C1 * BLK, 16);
+    else if (p == NT + 1) pipe.issue(W + IE_C1 * BLK, Z ? 8 : 16);
     else if (with_fn) pipe.issue(W + IE_NBR * BLK, MAT128);
     return w;
   };
+  if constexpr (Z) {
+    P32<2> zop;
+    init_tile_x32_z<GC>(acc, gop, a.wvec, lane, h, wt, [](int t) { return 8 * t; }, zop);
+    if (valid) store_z0(zop, reinterpret_cast<u16*>(a.f_out), e, h);
+    return;
+  }
   X32<4> f;
   init_tile_x32<GC>(acc, gop, a.wvec, lane, h, wt, [](int t) { return 8 * t; }, f);
   if (valid) store_row32(f, reinterpret_cast<u16*>(a.f_out) + (int64_t)e * HID, h);
@@ -918,6 +939,20 @@ __device__ __forceinline__ void x32_f_residual(X32<4>& x, const u16* w, const fl
   });
   pin(x);
 }
+// the same with F taken block by block from fblk(b) (an R32<1>: the z0 form rebuilds F0's blocks)
+template <class FB>
+__device__ __forceinline__ void x32_f_residual_blk(X32<4>& x, const u16* w, const float* v, FB&& fblk, int lane, int h) {
+  P32<8> op;
+  make_op32(op, x);
+  X32<4> y;
+  lin32_pipe<8>(y, op, w, v, lane, h, [&](int b) {
+    silu2_blk(y.v[b]);
+    const R32<1> fr = fblk(b);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) set_quad(x.v[b], q, unpack4(fr.u[q]) + silu2_unit<true>() * quad(y.v[b], q));
+  });
+  pin(x);
+}
 
 // ---- the node layer's attention aggregation folded into the edge layer (di_edge_layer_attn)
 // h_attn[v] = sum_{e in in(v)} alpha[e, head] * V[src e] / (sum_e alpha[e, head] + 1e-6)
@@ -999,9 +1034,15 @@ __device__ __forceinline__ void edge_attn_fold(const EdgeArgs& a, int e, bool va
 
 // One 32-row tile per wave through the whole edge layer: the stage sequence `st` (the 8-wave ring's
 // RingStages) hands out each weight stage in order (next(): its weights, v(): its bias).
-template <int MODE, bool GC, class ST>
-__device__ __forceinline__ void edge_x32_tile(const EdgeArgs& a, ST& st, int e, bool valid, int lane, int h) {
+// Z0 (layer 0 after k_init_x32<true, true>): a.f_in holds z0 rows (mfma32.h) and wc2 the 8 packed
+// blocks of InitEdge's combined_linear_2 in LDS. The row's z0 operand stays in 8 registers for the
+// whole tile and each 32-feature block of F0 is rebuilt from it where F is used (f0_blk: the MFMAs
+// and the rounding InitEdge applies), one block live at a time, instead of four reads of the F row.
+template <int MODE, bool GC, bool Z0, class ST>
+__device__ __forceinline__ void edge_x32_tile(const EdgeArgs& a, ST& st, int e, bool valid, int lane, int h,
+                                              const u16* wc2) {
   constexpr bool FINAL = MODE == 1;
+  static_assert(!Z0 || (GC && !FINAL), "the z0 form is the non-final DI_GRAPH_GEO_REF layer 0");
   const u16* f_row = reinterpret_cast<const u16*>(a.f_in) + (int64_t)e * HID;
   const u16* qkv = reinterpret_cast<const u16*>(a.qkv);
 
@@ -1019,8 +1060,15 @@ __device__ __forceinline__ void edge_x32_tile(const EdgeArgs& a, ST& st, int e, 
   }
   X32<4> x;
   R32<4> fr;  // the edge's own row F, re-read (L2) before each use: the stages have no room to hold it
+  P32<2> zop;  // Z0: the row's z0 operand instead
+  auto f0 = [&](int b) { return f0_blk(wc2, zop, b, lane); };
+  (void)f0;
   const u16* w;
-  if constexpr (GC) {
+  if constexpr (Z0) {
+    load_z0(zop, reinterpret_cast<const u16*>(a.f_in), e, h);
+    w = st.next([&] { asm volatile("" ::"v"(zop.f[0]), "v"(zop.f[1])); });  // orig_msg_linear (+ its bias)
+    init_vec32_lds(x, st.v(), h);
+  } else if constexpr (GC) {
     // DI_GRAPH_GEO_REF: the neighbour messages are multiplied by dir_linear_1(dir_linear_0(0)) = 0
     // (:408), so x = orig_msg_linear(F) + b exactly; no gathered rows, no stages 0-1
     fr.load(f_row, h);
@@ -1105,7 +1153,19 @@ __device__ __forceinline__ void edge_x32_tile(const EdgeArgs& a, ST& st, int e, 
   }
   {
     P32<8> fop;
-    raw_op32(fop, fr);
+    if constexpr (Z0) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        lean_fence();  // block by block: one rebuilt block live at a time
+        P32<2> o;
+        raw_op32(o, f0(b));
+        fop.f[2 * b] = o.f[0];
+        fop.f[2 * b + 1] = o.f[1];
+        asm volatile("" : "+v"(fop.f[2 * b]), "+v"(fop.f[2 * b + 1]));
+      }
+    } else {
+      raw_op32(fop, fr);
+    }
     mma32<4, 8>(x, fop, w, lane);
     pin(x);
   }
@@ -1113,9 +1173,10 @@ __device__ __forceinline__ void edge_x32_tile(const EdgeArgs& a, ST& st, int e, 
   x32_res_block(x, st, lane, h);
   // F rows are loaded BEFORE the stage's barrier and DMA issue: vmcnt retires in order, so a load
   // issued after the stage's LDS-DMA pieces would make its use wait for the whole weight stage
-  fr.load(f_row, h);
-  w = st.next([&] { settle(fr); });  // res_connect_linear: x = F + silu(rc(x))
-  x32_f_residual(x, w, st.v(), fr, lane, h);
+  if constexpr (!Z0) fr.load(f_row, h);
+  w = st.next([&] { if constexpr (!Z0) settle(fr); });  // res_connect_linear: x = F + silu(rc(x))
+  if constexpr (Z0) x32_f_residual_blk(x, w, st.v(), f0, lane, h);
+  else x32_f_residual(x, w, st.v(), fr, lane, h);
   x32_res_block(x, st, lane, h);
   x32_res_block(x, st, lane, h);
   w = st.next();  // final geometric gate [4x2]
@@ -1127,9 +1188,10 @@ __device__ __forceinline__ void edge_x32_tile(const EdgeArgs& a, ST& st, int e, 
     for (int b = 0; b < 4; ++b) x.v[b] *= fg.v[b];
     pin(x);
   }
-  fr.load(f_row, h);
-  w = st.next([&] { settle(fr); });  // final_linear: x = F + silu(final(x)) = conformation output
-  x32_f_residual(x, w, st.v(), fr, lane, h);
+  if constexpr (!Z0) fr.load(f_row, h);
+  w = st.next([&] { if constexpr (!Z0) settle(fr); });  // final_linear: x = F + silu(final(x)) = conformation output
+  if constexpr (Z0) x32_f_residual_blk(x, w, st.v(), f0, lane, h);
+  else x32_f_residual(x, w, st.v(), fr, lane, h);
 
   // ---- attention scores (propagate_attention :76-91): head hd = features 32 hd .. 32 hd + 31 = block hd
   R32<4> kr, qr;  // K[src], Q[dst], issued before the stage barrier
@@ -1138,7 +1200,7 @@ __device__ __forceinline__ void edge_x32_tile(const EdgeArgs& a, ST& st, int e, 
   qr.load(qkv + (int64_t)dn * 3 * HID, h);
   // the fold's V[src] row and the destination's in-edge range, in flight with K / Q (GEO_REF kernels;
   // the general path's extra live rows leave no room: loaded at the fold)
-  const bool fold = a.attn_out != nullptr;  // uniform
+  const bool fold = !Z0 && a.attn_out != nullptr;  // uniform (there is no fold form of the z0 layer)
   R32<4> vr;
   int2 ip = {0, 0};
   auto fold_loads = [&] {
@@ -1190,15 +1252,24 @@ __device__ __forceinline__ void edge_x32_tile(const EdgeArgs& a, ST& st, int e, 
     make_op32(pop, p);
     pin(pop);
     if (fold) edge_attn_fold(a, e, valid, lane, h, al, dn, vr, ip);  // p is packed: room for the scan
-    fr.load(f_row, h);                 // O_edge: re-read
-    w = st.next([&] { settle(fr); });  // O_edge_feats
+    if constexpr (!Z0) fr.load(f_row, h);                    // O_edge: re-read
+    w = st.next([&] { if constexpr (!Z0) settle(fr); });  // O_edge_feats
     X32<4> e1;
     init_vec32_lds(e1, st.v(), h);
     mma32<4, 8>(e1, pop, w, lane);
 #pragma unroll
-    for (int b = 0; b < 4; ++b)
+    for (int b = 0; b < 4; ++b) {
+      R32<1> fb;
+      if constexpr (Z0) {
+        lean_fence();
+        fb = f0(b);
+      } else {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) set_quad(e1.v[b], q, quad(e1.v[b], q) + unpack4(fr.u[4 * b + q]));
+        for (int q = 0; q < 4; ++q) fb.u[q] = fr.u[4 * b + q];
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) set_quad(e1.v[b], q, quad(e1.v[b], q) + unpack4(fb.u[q]));
+    }
     pin(e1);
     P32<8> eop;
     make_op32(eop, e1);
@@ -1390,7 +1461,14 @@ struct RingStagesT {
 template <int NS, bool GC>
 using RingStages = RingStagesT<EdgeRingSrc<NS, GC>>;
 
-template <int MODE, bool GC>
+// Z0 (di_edge_layer_z): layer 0 on z0 rows; InitEdge's combined_linear_2 (8 packed blocks, 8 KiB of
+// the kind-1 blob at IE_C1 + 8) stays in LDS beside the ring for the block's lifetime
+constexpr int Z0_WC2_BLOCKS = 8;
+static_assert(RING_SLOTS * RingSlot::SLOT_BYTES + 2 * RING_SLOTS * (int)sizeof(uint32_t) + Z0_WC2_BLOCKS * BLK * 2 <=
+                  160 * 1024,
+              "ring slots + counters + combined_linear_2 fit the CU's LDS (the pair stream uses none)");
+static_assert(Z0_WC2_BLOCKS == RING_NW, "one 1-KiB LDS-DMA piece of combined_linear_2 per wave");
+template <int MODE, bool GC, bool Z0 = false>
 __global__ __attribute__((amdgpu_flat_work_group_size(1, EdgeRingGeo::THREADS), amdgpu_waves_per_eu(2, 2),
                           amdgpu_num_vgpr(120)))
 void k_edge_x32_ring(EdgeArgs a, int ntiles) {
@@ -1402,6 +1480,15 @@ void k_edge_x32_ring(EdgeArgs a, int ntiles) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int my_tiles = ((int)blockIdx.x < ntiles) ? (ntiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
   if (threadIdx.x < 2 * RING_SLOTS) counters[threadIdx.x] = 0;
+  const u16* wc2 = nullptr;
+  if constexpr (Z0) {
+    __shared__ __attribute__((aligned(16))) u16 wc2_lds[Z0_WC2_BLOCKS * BLK];
+    dma_piece(rsrc_of(reinterpret_cast<const u16*>(a.init_wmat) + (IE_C1 + 8) * BLK),
+              (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)wc2_lds + wave * 1024, lane * 16,
+              wave * 1024);
+    lds_dma_wait();  // the barrier below does not wait for LDS-DMA
+    wc2 = wc2_lds;
+  }
   __syncthreads();
   RingStages<NS, GC> st{lds, counters, counters + RING_SLOTS, {reinterpret_cast<const u16*>(a.wmat), a.wvec}, wave,
                         my_tiles * NS};
@@ -1415,7 +1502,7 @@ void k_edge_x32_ring(EdgeArgs a, int ntiles) {
     const int r = tile * EdgeRingGeo::ROWS + wave * EdgeRingGeo::ROWS_PER_WAVE + (lane & 31);
     const bool valid = r < a.Et;
     const int e = valid ? r : a.Et - 1;
-    edge_x32_tile<MODE, GC>(a, st, e, valid, lane, h);
+    edge_x32_tile<MODE, GC, Z0>(a, st, e, valid, lane, h, wc2);
   }
 }
 
@@ -2456,6 +2543,26 @@ extern "C" int di_embed_init_edge(const di_graph* g, di_dtype dt, int32_t in_dim
   return launch_status();
 }
 
+extern "C" int di_embed_init_edge_z(const di_graph* g, di_dtype dt, int32_t in_dim, const float* node_f,
+                                    const void* embed_wmat, const float* embed_wvec, void* h_out, void* qkv_out,
+                                    const float* edge_f, const void* init_wmat, const float* init_wvec,
+                                    const float* pos_src_tab, const float* pos_dst_tab, void* z_out, void* queue,
+                                    int32_t signal_job, void* stream) {
+  if (!g || !(g->flags & DI_GRAPH_GEO_REF) || !g->src || !g->dst || !g->node_pos || g->num_nodes <= 0 ||
+      g->num_edges <= 0 || in_dim <= 0 || in_dim > HID || !node_f || !embed_wmat || !embed_wvec || !h_out ||
+      !qkv_out || !edge_f || !init_wmat || !init_wvec || !pos_src_tab || !pos_dst_tab || !z_out || dt != DI_BF16)
+    return DI_EINVAL;
+  EmbedArgs ea{g->num_nodes, in_dim, node_f, embed_wmat, embed_wvec, h_out, qkv_out, (uint32_t*)queue, signal_job};
+  // z_out in f_out's place (k_init_x32<true, true>)
+  InitArgs a{g->num_edges, edge_f, g->src, g->dst, g->node_pos, init_wmat, init_wvec, pos_src_tab, pos_dst_tab,
+             z_out, nullptr};
+  const int eb = (ea.Nt + InitX32Geo::EMBED_ROWS - 1) / InitX32Geo::EMBED_ROWS;
+  const int ib = (a.Et + InitX32Geo::ROWS - 1) / InitX32Geo::ROWS;
+  hipLaunchKernelGGL((k_init_x32<true, true>), dim3((unsigned)(eb + ib)), dim3(InitX32Geo::THREADS), 0,
+                     (hipStream_t)stream, a, ea, eb);
+  return launch_status();
+}
+
 extern "C" int di_init_edge_resident(const di_graph* g, const float* edge_f, const void* wmat, const float* wvec,
                                      const float* pos_src_tab, const float* pos_dst_tab, void* f_out, void* stream) {
   if (!g || !(g->flags & DI_GRAPH_GEO_REF) || !g->src || !g->dst || !g->node_pos || !edge_f || !wmat || !wvec ||
@@ -2511,6 +2618,22 @@ extern "C" int di_edge_layer(const di_graph* g, di_dtype dt, int final_layer, co
                              void* stream) {
   return edge_layer(g, dt, final_layer, edge_f, f_in, fn_in, qkv, wmat, wvec, alpha_out, f_out, fn_out, nullptr,
                     nullptr, stream);
+}
+
+extern "C" int di_edge_layer_z(const di_graph* g, di_dtype dt, const float* edge_f, const void* z_in,
+                               const void* init_wmat, const void* qkv, const void* wmat, const float* wvec,
+                               float* alpha_out, void* f_out, void* stream) {
+  // the non-final bf16 DI_GRAPH_GEO_REF layer 0 of edge_layer(), F0 rebuilt from z0 rows
+  if (!g || !(g->flags & DI_GRAPH_GEO_REF) || !edge_f || !z_in || !init_wmat || !qkv || !wmat || !wvec || !f_out ||
+      !g->src || !g->dst || g->num_edges <= 0 || dt != DI_BF16)
+    return DI_EINVAL;
+  EdgeArgs a{g->num_edges, edge_f, g->src, g->dst, g->nbr, z_in, nullptr, qkv, wmat, wvec, alpha_out,
+             f_out, nullptr, nullptr, nullptr, g->in_ptr, init_wmat};
+  const int ntiles = (a.Et + EdgeRingGeo::ROWS - 1) / EdgeRingGeo::ROWS;
+  const int cus = device_cus();
+  const dim3 grid((unsigned)(ntiles < cus ? ntiles : cus)), block(EdgeRingGeo::THREADS);
+  hipLaunchKernelGGL((k_edge_x32_ring<0, true, true>), grid, block, 0, (hipStream_t)stream, a, ntiles);
+  return launch_status();
 }
 
 extern "C" int64_t di_attn_parts_bytes(int32_t num_edges) {

@@ -51,6 +51,24 @@ struct R32 {
   }
 };
 
+// The z0 row (k_init_x32<true, true> -> k_edge_x32_ring<0, true, true>): an edge's 32-feature
+// combined_linear_1 output, stored as the packed operand P32<2> the writer's lanes hold, not in
+// feature order. Row e, lane half h at byte 64 e + 32 h; the lane's 32 B are two 16-B pieces,
+// f[0] then f[1], so a wave's 32 rows are one contiguous 2 KiB. bf16 element 16 h + 8 s + j of the
+// row is feature 16 s + 8 (j >> 2) + 4 h + (j & 3) (the k order of the header comment). The layout is
+// private to those two kernels.
+constexpr int Z0_ROW = 32;  // bf16 elements per z0 row
+__device__ __forceinline__ void load_z0(P32<2>& z, const u16* zbuf, int64_t e, int h) {
+  const u16* p = zbuf + e * Z0_ROW + 16 * h;
+  z.f[0] = *reinterpret_cast<const bf16x8*>(p);
+  z.f[1] = *reinterpret_cast<const bf16x8*>(p + 8);
+}
+__device__ __forceinline__ void store_z0(const P32<2>& z, u16* zbuf, int64_t e, int h) {
+  u16* p = zbuf + e * Z0_ROW + 16 * h;
+  *reinterpret_cast<bf16x8*>(p) = z.f[0];
+  *reinterpret_cast<bf16x8*>(p + 8) = z.f[1];
+}
+
 __device__ __forceinline__ floatx4 unpack4(uint2 u) {
   return (floatx4){__builtin_bit_cast(float, u.x << 16), __builtin_bit_cast(float, u.x & 0xffff0000u),
                    __builtin_bit_cast(float, u.y << 16), __builtin_bit_cast(float, u.y & 0xffff0000u)};
@@ -165,6 +183,22 @@ __device__ __forceinline__ floatx16 mfma32(const bf16x8& a, const bf16x8& b, con
 }
 __device__ __forceinline__ bf16x8 afrag(const u16* w, int blk, int lane) {
   return *reinterpret_cast<const bf16x8*>(w + blk * BLK + lane * 8);
+}
+
+// Block b of the row F0 = combined_linear_2(z0) in its storage format, from the z0 operand and the 8
+// packed blocks of combined_linear_2 in LDS: the two MFMAs mma32<4, 2> issues for output block b
+// (k-step 0, then 1, from zero) and store_row32's rounding, i.e. the bits InitEdge would have stored.
+__device__ __forceinline__ R32<1> f0_blk(const u16* wc2, const P32<2>& z, int b, int lane) {
+  floatx16 fb = {};
+  fb = mfma32(afrag(wc2, 2 * b, lane), z.f[0], fb);
+  fb = mfma32(afrag(wc2, 2 * b + 1, lane), z.f[1], fb);
+  R32<1> r;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const floatx4 x = quad(fb, q);
+    r.u[q] = (uint2){pack_bf16x2(x[0], x[1]), pack_bf16x2(x[2], x[3])};
+  }
+  return r;
 }
 
 // out (NBO 32-feature blocks) += W (NBO x NS packed blocks in LDS, block (ob, s) at ob*NS + s) . op,

@@ -4,6 +4,8 @@ Per batch of chains (one launch per stage covers every chain of the batch):
 
     di_node_embed                    h0, QKV(layer 0)
     di_init_edge                     F0 = InitEdge(G), Fn0 = nbr_linear_0(F0)
+    (bf16 reference-featurised batches, L >= 2: di_embed_init_edge_z + di_edge_layer_z for these
+     and layer 0's edge layer -- GeoTEngine.z_init)
     for layer l < L-1:
         di_edge_layer(intermediate)  alpha_l, F_{l+1}, Fn_{l+1}
         di_node_layer(intermediate)  h_{l+1}, QKV(layer l+1)
@@ -16,6 +18,7 @@ returned edge features are the last INTERMEDIATE layer's (the final layer update
 from __future__ import annotations
 
 import ctypes
+import os
 
 import torch
 
@@ -70,6 +73,15 @@ class _Ticker:
         self.name, self.start = name, ev
 
 
+def uses_z_init(eng, gb) -> bool:
+    """Whether a forward of `eng` over `gb` takes the z0 path (GeoTEngine.z_init): InitEdge stores
+    its 32-wide factor and layer 0 rebuilds F0 from it. bf16 reference-featurised batches through the
+    fused embedding + InitEdge launch only, without the folded aggregation, and only when layer 0 is
+    not the final layer (which has no edge output to rebuild F0 for)."""
+    return bool(eng.z_init and eng.dtype == "bf16" and gb.geo_ref and eng.fuse_embed_init
+                and not eng.fold_attn and eng.packed.num_layers >= 2)
+
+
 class GeoTEngine:
     """Holds packed device weights; runs the GeoT forward for a GraphBatch."""
 
@@ -104,6 +116,12 @@ class GeoTEngine:
         # staged di_init_edge. The resident block cannot share a SIMD with a pair-stream wave, so the
         # overlapped schedule needs it off (pipeline.OverlappedSchedule checks)
         self.resident_init = True
+        # InitEdge's edge output kept as z0, the 32-wide combined_linear_1 output (64 B per edge instead
+        # of the 256-B F0 row); layer 0's edge kernel rebuilds F0 = combined_linear_2(z0) in registers,
+        # bit-identically (di_embed_init_edge_z + di_edge_layer_z; where it applies: uses_z_init).
+        # DI_INIT_Z=0 in the environment turns it off (read once, here)
+        self.z_init = os.environ.get("DI_INIT_Z", "1") != "0"
+        self.z_forwards = 0  # forwards that took the z0 path
 
     def _check_blob_sizes(self):
         p, dt = self.packed, _DI_DT[self.dtype]
@@ -144,6 +162,7 @@ class GeoTEngine:
                 "qkv": [torch.empty(cn, 3 * H, dtype=dt, device=dev) for _ in range(2)],
                 "f": [torch.empty(ce, H, dtype=dt, device=dev) for _ in range(2)],
                 "fn": [torch.empty(ce, H, dtype=dt, device=dev) for _ in range(2)],
+                "z0": torch.empty(ce, 32, dtype=torch.bfloat16, device=dev) if self.dtype == "bf16" else None,
                 "alpha": torch.empty(ce, 4, dtype=torch.float32, device=dev),
                 "attn": torch.empty(cn, H, dtype=torch.float32, device=dev),
                 "parts": torch.empty(max(self.lib.di_attn_parts_bytes(ce), 4) // 4, dtype=torch.float32, device=dev),
@@ -156,6 +175,7 @@ class GeoTEngine:
             "f": [t[:num_edges] for t in b["f"]], "fn": [t[:num_edges] for t in b["fn"]],
             "alpha": b["alpha"][:num_edges], "attn": b["attn"][:num_nodes], "parts": b["parts"],
             "hT": b["hT"][:H * num_nodes].view(H, num_nodes),
+            "z0": b["z0"][:num_edges] if b["z0"] is not None else None,
         }
         return views
 
@@ -168,7 +188,11 @@ class GeoTEngine:
         input; default: the slot's own). Either way it is self.last_hT afterwards.
         signal: optional (pair-queue state tensor, job): this forward's first launch marks `job` ready
         at its start -- a previous forward's hT, complete by stream order (include/deepinteract_amd.h,
-        pair-tensor queue: the signal_job argument)."""
+        pair-tensor queue: the signal_job argument).
+
+        On the z0 path (uses_z_init) the slot's f[0] is not written: InitEdge's output lives in the
+        slot's z0 and layer 0 writes f[1]. Nothing reads f[0] after a forward (the returned edge
+        features are f[(L-1) % 2] with L >= 2 there)."""
         lib, p, dt = self.lib, self.packed, _DI_DT[self.dtype]
         check_on(self.device, "GeoTEngine.forward", gb.src, gb.dst, gb.nbr, gb.node_f, gb.edge_f,
                  gb.node_pos, gb.in_ptr, hT_out)
@@ -191,7 +215,15 @@ class GeoTEngine:
             fn = [None, None]
         sq, sjob = (_ptr(signal[0]), int(signal[1])) if signal is not None else (_ptr(None), -1)
         tick = _Ticker(events)
-        if self.fuse_embed_init and gb.geo_ref:
+        use_z = uses_z_init(self, gb)
+        self.z_forwards += use_z
+        if use_z:
+            tick("init_edge")
+            _lib.check(lib.di_embed_init_edge_z(g, dt, gb.node_f.shape[1], _ptr(gb.node_f), _ptr(p.embed[0]),
+                                                _ptr(p.embed[1]), _ptr(h[0]), _ptr(qkv[0]), _ptr(gb.edge_f),
+                                                _ptr(p.init[0]), _ptr(p.init[1]), _ptr(p.pos_src), _ptr(p.pos_dst),
+                                                _ptr(ws["z0"]), sq, sjob, st), "di_embed_init_edge_z")
+        elif self.fuse_embed_init and gb.geo_ref:
             tick("init_edge")
             _lib.check(lib.di_embed_init_edge(g, dt, gb.node_f.shape[1], _ptr(gb.node_f), _ptr(p.embed[0]), _ptr(p.embed[1]),
                                               _ptr(h[0]), _ptr(qkv[0]), _ptr(gb.edge_f), _ptr(p.init[0]),
@@ -236,10 +268,14 @@ class GeoTEngine:
                     f_out = nxt
                 cur = nxt
                 continue
-            _lib.check(lib.di_edge_layer(g, dt, int(final), _ptr(gb.edge_f), _ptr(f[cur]), _ptr(fn[cur]),
-                                         _ptr(qkv[cur]), _ptr(em), _ptr(ev), _ptr(alpha),
-                                         _ptr(None if final else f[nxt]), _ptr(None if final else fn[nxt]),
-                                         st), "di_edge_layer")
+            if use_z and li == 0:
+                _lib.check(lib.di_edge_layer_z(g, dt, _ptr(gb.edge_f), _ptr(ws["z0"]), _ptr(p.init[0]), _ptr(qkv[cur]),
+                                               _ptr(em), _ptr(ev), _ptr(alpha), _ptr(f[nxt]), st), "di_edge_layer_z")
+            else:
+                _lib.check(lib.di_edge_layer(g, dt, int(final), _ptr(gb.edge_f), _ptr(f[cur]), _ptr(fn[cur]),
+                                             _ptr(qkv[cur]), _ptr(em), _ptr(ev), _ptr(alpha),
+                                             _ptr(None if final else f[nxt]), _ptr(None if final else fn[nxt]),
+                                             st), "di_edge_layer")
             if self.split_node:
                 # CSR segment reduction of the attention messages, then O_node / FFN / next Q,K,V
                 tick("node_aggr")

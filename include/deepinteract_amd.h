@@ -151,6 +151,28 @@ int di_edge_layer(const di_graph* g, di_dtype dt, int final_layer, const float* 
                   const void* f_in, const void* fn_in, const void* qkv,
                   const void* wmat, const float* wvec,
                   float* alpha_out /*[Et,4]*/, void* f_out, void* fn_out, void* stream);
+/* The bf16 DI_GRAPH_GEO_REF pair InitEdge -> non-final layer 0 without the [Et,128] row F0 between
+ * them (an addition to ABI 8). F0 = combined_linear_2(z0) with z0 InitEdge's 32-wide
+ * combined_linear_1 output, so:
+ *   di_embed_init_edge_z = di_embed_init_edge (queue / signal_job included) storing z0 instead of F0:
+ *     z_out is [Et,32] bf16 (64 B per edge, a quarter of the F0 row) in the kernels' packed operand
+ *     order -- element 16 h + 8 s + j of a row is z0 feature 16 s + 8 (j >> 2) + 4 h + (j & 3), for
+ *     h, s in {0,1}, j < 8; features 28..31 are zero padding. Private to this pair of entry points.
+ *   di_edge_layer_z = di_edge_layer(final_layer = 0) reading z_in (those rows) and init_wmat (the
+ *     kind-1 bf16 blob InitEdge ran with) instead of f_in: each 32-feature block of F0 is rebuilt in
+ *     registers where the layer uses it -- the MFMAs and the bf16 rounding InitEdge applies -- so
+ *     alpha_out and f_out are bit-identical to di_embed_init_edge + di_edge_layer. alpha_out may be
+ *     NULL (not written).
+ * DI_EINVAL unless dt == DI_BF16 and the graph has DI_GRAPH_GEO_REF. There is no di_edge_layer_attn
+ * form. */
+int di_embed_init_edge_z(const di_graph* g, di_dtype dt, int32_t in_dim, const float* node_f /*[Nt,in_dim]*/,
+                         const void* embed_wmat, const float* embed_wvec, void* h_out /*[Nt,128]*/,
+                         void* qkv_out /*[Nt,384]*/, const float* edge_f, const void* init_wmat,
+                         const float* init_wvec, const float* pos_src_tab, const float* pos_dst_tab,
+                         void* z_out /*[Et,32] bf16*/, void* queue, int32_t signal_job, void* stream);
+int di_edge_layer_z(const di_graph* g, di_dtype dt, const float* edge_f, const void* z_in /*[Et,32] bf16*/,
+                    const void* init_wmat /*kind-1 bf16 blob*/, const void* qkv, const void* wmat,
+                    const float* wvec, float* alpha_out /*[Et,4]*/, void* f_out /*[Et,128]*/, void* stream);
 
 /* hT_out (optional, may be NULL): also write h_out transposed, [128, Nt] (pair-tensor input).
  * bf16: DI_ERANGE when Nt * 768 or Et * 16 reaches 2^31 (the segment sums use 32-bit byte offsets;

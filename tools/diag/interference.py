@@ -5,7 +5,8 @@ one forward is run first). Per background kind: the pair stream's rate over the 
 background covers, and the background kernel's mean duration beside it, vs both alone.
 
 usage (GPU box): python tools/diag/interference.py [--jobs 12]
-One JSON line per background kind (none, init, init_res, edge0, node0, edge1, node1).
+One JSON line per background kind (none, init, init_res, edge0, node0, edge1, node1; with --only
+also init_z / edge0_z, the z0 forms: di_embed_init_edge_z / di_edge_layer_z).
 """
 import argparse
 import ctypes
@@ -47,6 +48,15 @@ def main():
             rc = lib.di_embed_init_edge(g, dt, gb.node_f.shape[1], _ptr(gb.node_f), _ptr(p.embed[0]), _ptr(p.embed[1]),
                                         _ptr(h[0]), _ptr(qkv[0]), _ptr(gb.edge_f), _ptr(p.init[0]), _ptr(p.init[1]),
                                         _ptr(p.pos_src), _ptr(p.pos_dst), _ptr(f[0]), _ptr(None), -1, st)
+        elif kind == "init_z":
+            rc = lib.di_embed_init_edge_z(g, dt, gb.node_f.shape[1], _ptr(gb.node_f), _ptr(p.embed[0]),
+                                          _ptr(p.embed[1]), _ptr(h[0]), _ptr(qkv[0]), _ptr(gb.edge_f), _ptr(p.init[0]),
+                                          _ptr(p.init[1]), _ptr(p.pos_src), _ptr(p.pos_dst), _ptr(ws["z0"]), _ptr(None),
+                                          -1, st)
+        elif kind == "edge0_z":
+            em, ev = p.edge[0]
+            rc = lib.di_edge_layer_z(g, dt, _ptr(gb.edge_f), _ptr(ws["z0"]), _ptr(p.init[0]), _ptr(qkv[0]), _ptr(em),
+                                     _ptr(ev), _ptr(alpha), _ptr(f[1]), st)
         elif kind == "init_res":
             rc = lib.di_init_edge_resident(g, _ptr(gb.edge_f), _ptr(p.init[0]), _ptr(p.init[1]), _ptr(p.pos_src),
                                            _ptr(p.pos_dst), _ptr(f[0]), st)
@@ -61,6 +71,12 @@ def main():
             rc = lib.di_node_layer(g, dt, li, _ptr(alpha), _ptr(h[li]), _ptr(qkv[li]), _ptr(nm), _ptr(nv),
                                    _ptr(h[1 - li]), _ptr(None if li else qkv[1]), _ptr(hT if li else None), st)
         _lib.check(rc, kind)
+
+    # the forward may have kept InitEdge's output as z0 only (GeoTEngine.z_init): both forms' inputs
+    st0 = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    launch("init", st0)
+    launch("init_z", st0)
+    torch.cuda.synchronize()
 
     # pair jobs: C3 micro-batches reading this batch's hT
     n_rows = gb.num_nodes
@@ -138,7 +154,8 @@ def main():
     # enough launches to cover ~80 % of the pair window (pair ~1 ms per job beside)
     kinds = sys.argv[sys.argv.index("--only") + 1].split(",") if "--only" in sys.argv else \
         ["init", "init_res", "edge0", "node0", "edge1", "node1"]
-    est = {"init": 140, "init_res": 140, "edge0": 430, "node0": 52, "edge1": 330, "node1": 45}
+    est = {"init": 140, "init_z": 140, "init_res": 140, "edge0": 430, "edge0_z": 430, "node0": 52, "edge1": 330,
+           "node1": 45}
     for kind in kinds:
         us = est[kind]
         print(json.dumps(beside(kind, 800.0 / us)), flush=True)
