@@ -10,7 +10,7 @@ from deepinteract_amd import build
 
 VARIANTS = {
     # the product library's compile-time knobs, each kept tested by a -m gpu test against its variant:
-    # k_node_layer in 2-wave blocks (csrc/geot_kernels.hip DI_NODE_NW; every launch site takes its shape
+    # k_node_layer in 2-wave blocks (csrc/geot_node.hip DI_NODE_NW; every launch site takes its shape
     # from NodeGeo; tests/test_gpu_variants.py, tests/test_gpu_node_aggr.py via DI_TEST_VARIANT)
     "node2": ["DI_NODE_NW=2"],
     # fp32 SiLU as libm expf + IEEE division (csrc/common.h DI_F32_FAST_SILU; the round-2 default)

@@ -1,7 +1,8 @@
-"""Compile geot_kernels.hip to gfx950 assembly with extra -D defines and print, per kernel, the
-register/scratch use and a one-letter instruction-class trace of each basic block (M mfma, D ds,
-G vmem, w waitcnt, B barrier, v valu, s salu): where the waits sit relative to the MFMAs.
-usage: python tools/diag/isa_view.py [-DNAME=V ...] [--kernel REGEX] [--trace]"""
+"""Compile one GeoT stage file (csrc/geot_<stage>.hip; stage: init, edge or node, default edge) to
+gfx950 assembly with extra -D defines and print, per kernel, the register/scratch use and a
+one-letter instruction-class trace of each basic block (M mfma, D ds, G vmem, w waitcnt, B barrier,
+v valu, s salu): where the waits sit relative to the MFMAs.
+usage: python tools/diag/isa_view.py [-DNAME=V ...] [--stage STAGE] [--kernel REGEX] [--trace]"""
 import os
 import re
 import subprocess
@@ -10,9 +11,10 @@ import sys
 R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 defs = [a for a in sys.argv[1:] if a.startswith("-D")]
 kre = re.compile(sys.argv[sys.argv.index("--kernel") + 1] if "--kernel" in sys.argv else r"k_edge_layerINS_5BF16TELi0E")
+stage = sys.argv[sys.argv.index("--stage") + 1] if "--stage" in sys.argv else "edge"
 out = "/tmp/isa_view.s"
 subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--offload-device-only", "-S",
-                f"-I{R}/include", *defs, f"{R}/deepinteract_amd/csrc/geot_kernels.hip", "-o", out], check=True,
+                f"-I{R}/include", *defs, f"{R}/deepinteract_amd/csrc/geot_{stage}.hip", "-o", out], check=True,
                stderr=subprocess.DEVNULL)
 s = open(out).read()
 
