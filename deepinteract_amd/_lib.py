@@ -48,6 +48,13 @@ class DiPairJob(ctypes.Structure):
                 ("items", ctypes.c_int32)]
 
 
+class DiRankMetrics(ctypes.Structure):
+    _fields_ = [("num_pos", ctypes.c_int64), ("tp", ctypes.c_int64), ("fp", ctypes.c_int64),
+                ("fn", ctypes.c_int64), ("tn", ctypes.c_int64), ("ce_sum", ctypes.c_double)]
+
+
+DI_RANK_MAX_K = 4096
+
 # pair-queue words (include/deepinteract_amd.h, di_pair_queue_bytes)
 PQ_READY, PQ_ERROR, PQ_GAVE_UP, PQ_SBYTES, PQ_HBYTES = 0, 32, 33, 40, 42
 
@@ -92,6 +99,8 @@ _SIGS = {
     "di_inorm_work_bytes": ([_I, ctypes.c_int64], ctypes.c_int64),
     "di_se_scale_add": ([_I, _P, _P, _P, _P, _I, ctypes.c_int64, _P, _P], ctypes.c_int),
     "di_channel_mean": ([_I, _P, _I, ctypes.c_int64, _P, _P, _P, _P], ctypes.c_int),
+    "di_contact_rank_work_bytes": ([ctypes.c_int64, _I], ctypes.c_int64),
+    "di_contact_rank": ([_I, _P, _I, _I, _I, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
     "di_knn_topk": ([_I, _P, _P, _I, _I, _P, _P, _P], ctypes.c_int),
     "di_geo_feats": ([ctypes.POINTER(DiGeoArgs), _P], ctypes.c_int),
     "di_build_nbr_ids": ([_I, _P, _P, _P, ctypes.c_uint64, _P, _P], ctypes.c_int),

@@ -6,8 +6,9 @@ Mirrors the Python API the reference's hot path exposes (deepinteract_modules.py
   edata['f'] [E,28], edata['src_nbr_e_ids'|'dst_nbr_e_ids'] [E,2]; writes ndata['f'] [N,128]
   and edata['f'] [E,128] (the last intermediate layer's edges) in place, keeps batch_num_*.
 * ``LitGINI`` (:1478): ``gnn_forward`` (:1660-1679), ``shared_step`` (:1687-1745),
-  ``predict_step`` (:2178-2184), plus ``predict_batch`` (the batched entry the benchmark and the
-  distributed driver use).
+  ``predict_step`` (:2178-2184), ``test_step`` (:2018-2101), plus ``predict_batch`` (the batched
+  entry the benchmark and the distributed driver use) and ``predict_contacts`` (the same with each
+  complex's ranked contacts).
 
 Graphs may be ``deepinteract_amd.graph.ResidueGraph`` or real ``dgl.DGLGraph`` objects.
 Batched graphs get per-chain semantics (each chain as the reference computes it at batch size 1).
@@ -23,6 +24,7 @@ from .config import GeoTConfig, NODE_COUNT_LIMIT, RESIDUE_COUNT_LIMIT
 from .engine import GeoTEngine, HeadPrologueOp, PairTensorOp, gpu_device
 from .graph import GraphBatch, ResidueGraph, batch as batch_graphs, unbatch
 from .head import HeadNormOps, ResNet2DInputWithOptAttention, contact_probs
+from .ranking import ContactRankOp, labels_from_examples, topk_metrics
 
 
 def _identity_embedding_sd(sd, cfg: GeoTConfig):
@@ -82,7 +84,7 @@ class LitGINI(nn.Module):
                  num_gnn_attention_heads=4, knn=20, num_interact_layers=14, num_interact_hidden_channels=128,
                  num_classes=2, max_num_graph_nodes=NODE_COUNT_LIMIT, max_num_residues=RESIDUE_COUNT_LIMIT,
                  dtype="f32", head_dtype=torch.float32, precise_head=False, fuse_head_prologue=False,
-                 head_channels_last=False, head_hip_ops=True, **kwargs):
+                 head_channels_last=False, head_hip_ops=True, pos_prob_threshold=0.5, **kwargs):
         super().__init__()
         if num_gnn_hidden_channels != 128 or num_gnn_attention_heads != 4:
             # Q/K/V are Linear(H, H) whatever the head count, so a checkpoint trained with another
@@ -115,11 +117,15 @@ class LitGINI(nn.Module):
         # (head.HeadNormOps; NCHW only, so not with head_channels_last)
         self.head_hip_ops = head_hip_ops and not head_channels_last
         self.max_num_residues = max_num_residues
+        # pos_prob_threshold: a contact is predicted where its probability reaches it (test_step's
+        # rounded predictions and confusion counts; the reference's default)
+        self.pos_prob_threshold = float(pos_prob_threshold)
         self.interact_module = ResNet2DInputWithOptAttention(num_interact_layers, 2 * num_gnn_hidden_channels,
                                                              num_interact_hidden_channels, num_classes)
         self._geot_sd = None     # GeoT part of the reference state dict (host copy)
         self._prologue_w = None  # fp32 host copies of conv2d_1 / inorm_1 (fused head prologue)
         self._dev_ops = None     # (device, GeoTEngine, PairTensorOp, HeadPrologueOp | None)
+        self._rank_op = None     # ContactRankOp on the model's device
 
     def load_reference_state_dict(self, sd):
         """Reference-keyed LitGINI state dict. The head loads into this nn.Module; the GeoT
@@ -259,6 +265,59 @@ class LitGINI(nn.Module):
         """pairs: (chain-1 graph index, chain-2 graph index) per complex -> (logits, probs)."""
         logits, _, _ = self._forward_batch(gb, pairs)
         return logits, [contact_probs(lg) for lg in logits]
+
+    def _ranker(self):
+        dev = self.engine.device
+        if self._rank_op is None or self._rank_op.device != dev:
+            self._rank_op = ContactRankOp(dev)
+        return self._rank_op
+
+    def predict_contacts(self, gb: GraphBatch, pairs, k=None):
+        """predict_batch with each complex's ranked contacts: (logits, [ranking.ContactRanking]) --
+        the probability map, the k best contacts (default k = min(L1, L2)) as flat ids, (i, j) pairs
+        and scores; probability descending, ties by ascending index, NaN first (ranking.py)."""
+        logits, _, _ = self._forward_batch(gb, pairs)
+        rank = self._ranker()
+        return logits, [rank(lg.contiguous(), k=k) for lg in logits]
+
+    def test_step(self, batch, batch_idx=0):
+        """LitGINI.test_step (deepinteract_modules.py:2018-2101). batch = (graph1, graph2,
+        examples_list, filepaths); examples_list[i] is complex i's [L1 * L2, 3] (i, j, label) rows,
+        every pair exactly once. As in the reference, the figures are those of one complex per batch;
+        for a batch of several this returns the first complex's top-k figures and maps, and loss and
+        confusion over all of them.
+
+        Returns the reference's keys this build computes: loss (mean cross-entropy), top_10_prec,
+        top_l_by_10_prec, top_l_by_5_prec, top_l_recall, top_l_by_2_recall, top_l_by_5_recall
+        (l = min(L1, L2); float('nan') where the reference would divide by zero, ranking.topk_metrics),
+        test_preds / test_preds_rounded / test_labels as [L1, L2] numpy arrays, target, and
+        confusion = {tp, fp, fn, tn} at pos_prob_threshold. Out of scope: torchmetrics' test_acc /
+        test_prec / test_recall / test_f1 / test_auroc / test_auprc (the confusion counts are what the
+        first four are computed from)."""
+        import os
+        graph1, graph2, examples_list, filepaths = batch[0], batch[1], batch[2], batch[3]
+        logits_list = self.shared_step(graph1, graph2)
+        if len(examples_list) != len(logits_list):
+            raise ValueError("test_step: one examples tensor per complex")
+        rank = self._ranker()
+        results = []
+        for logits, examples in zip(logits_list, examples_list):
+            l1, l2 = int(logits.shape[2]), int(logits.shape[3])
+            labels = labels_from_examples(examples.to(rank.device), l1, l2)
+            results.append((rank(logits.contiguous(), k=min(l1, l2), labels=labels,
+                                 threshold=self.pos_prob_threshold), labels, l1, l2))
+        r0, labels0, l1, l2 = results[0]
+        n_all = sum(a * b for _, _, a, b in results)
+        confusion = {f: sum(getattr(r, f) for r, _, _, _ in results) for f in ("tp", "fp", "fn", "tn")}
+        out = {"loss": sum(r.ce_sum for r, _, _, _ in results) / n_all}
+        out.update(topk_metrics(r0.hits.cpu(), r0.num_pos, min(l1, l2)))
+        preds = r0.probs
+        out["test_preds"] = preds.cpu().numpy()
+        out["test_preds_rounded"] = (preds >= self.pos_prob_threshold).float().cpu().numpy()
+        out["test_labels"] = labels0.view(l1, l2).float().cpu().numpy()
+        out["target"] = str(filepaths[0]).split(os.sep)[-1][:4]
+        out["confusion"] = confusion
+        return out
 
 
 def construct_interact_tensor(graph1_feats, graph2_feats, pad=False, max_len=256):

@@ -31,6 +31,8 @@
  *                                                                    deepinteract_utils.py:474-530
  *   di_build_nbr_ids  per-edge neighbour-edge ids                    deepinteract_utils.py:534-553
  *   di_build_nbr_ids_torch  the same, bit-exact with torch.randperm  deepinteract_utils.py:539-546
+ *   di_contact_rank  LitGINI.test_step's softmax, ranking and counters deepinteract_modules.py:2018-2101,
+ *                                                                    deepinteract_utils.py:977-995
  *
  * Module-at-a-time entry points (deepinteract_amd/layers.py; same math as the fused kernels):
  *   di_conformation   ConformationModule.forward                      deepinteract_modules.py:373-455
@@ -345,6 +347,35 @@ int di_se_scale_add(di_dtype dt, const void* x, const float* scale, const float*
  * work: di_inorm_work_bytes() bytes. */
 int di_channel_mean(di_dtype dt, const void* x, int32_t channels, int64_t hw, const float* bias, void* work,
                     float* mean, void* stream);
+
+/* ---- contact ranking (an addition to ABI 8) ------------------------------------------------
+ * What LitGINI.test_step does with one complex's logits (deepinteract_modules.py:2018-2101; top-k
+ * precision / recall deepinteract_utils.py:977-995), without sorting the map. logits: [1, 2, l1, l2]
+ * contiguous NCHW in `dtype`, n = l1 * l2 (the class-1 plane starts at element n, any alignment).
+ *   probs [n] fp32       p = softmax(logits)[1] = 1 / (1 + exp(l0 - l1)), computed in fp32 (values
+ *                        below FLT_MIN may be flushed to 0; a NaN is stored as the positive quiet
+ *                        NaN 0x7fc00000); 16-B aligned
+ *   top_ids [k] int32    flat indices i * l2 + j of the k best contacts: p descending, equal p by
+ *                        ascending index, NaN above every number (what torch.sort(descending=True,
+ *                        stable=True) of probs gives); top_scores [k] fp32 their p
+ * labels [n] uint8 0/1 (NULL: none; then top_hits and metrics are NULL too):
+ *   top_hits [k] int32   positives among ranks 0 .. r
+ *   metrics (device)     num_pos and the confusion counts of (p >= threshold) against the labels;
+ *                        ce_sum = sum over all elements of -log softmax(logits)[label] in fp64
+ *                        (nn.CrossEntropyLoss in sum form; mean = ce_sum / n)
+ * work: di_contact_rank_work_bytes bytes, 16-B aligned; cleared in-stream by the call, so calls
+ * that share it need only stream order. Outputs are bit-reproducible from run to run.
+ * DI_EINVAL: n < 1, k < 1, k > n, bad dtype, a NULL required pointer, labels / top_hits / metrics
+ * not all NULL or all set, threshold NaN, probs or work not 16-B aligned. DI_ERANGE:
+ * k > DI_RANK_MAX_K, n >= 2^29 (the fp32 map stays under 2^31 bytes, as the pair tensor's planes).
+ * di_contact_rank_work_bytes returns the same -1 / -2. */
+typedef struct { int64_t num_pos, tp, fp, fn, tn; double ce_sum; } di_rank_metrics;
+#define DI_RANK_MAX_K 4096   /* the model's chain limit: the reference's largest k is l = min(L1, L2) */
+int64_t di_contact_rank_work_bytes(int64_t n, int32_t k);
+int di_contact_rank(int32_t dtype, const void* logits, int32_t l1, int32_t l2, int32_t k,
+                    const uint8_t* labels, float threshold, float* probs, int32_t* top_ids,
+                    float* top_scores, int32_t* top_hits, di_rank_metrics* metrics,
+                    void* work, void* stream);
 
 /* ---- graph builder ----------------------------------------------------------------------- */
 /* Cα kNN per chain: idx_out [Nt,k] chain-local neighbour ids (ascending squared distance,
