@@ -489,8 +489,11 @@ struct WPipe {
   int pend_n;
   const float* pendv;
   int pendv_n;
+  const T* pend2;  // a second run of blocks of the pending stage (issue2), behind the first in the slot
+  int pend2_n;
   __device__ explicit WPipe(void* lds)
-      : base(reinterpret_cast<char*>(lds)), cur(0), pend(nullptr), pend_n(0), pendv(nullptr), pendv_n(0) {}
+      : base(reinterpret_cast<char*>(lds)), cur(0), pend(nullptr), pend_n(0), pendv(nullptr), pendv_n(0),
+        pend2(nullptr), pend2_n(0) {}
   __device__ __forceinline__ T* slot_w(int s) const { return reinterpret_cast<T*>(base + (DBUF ? s : 0) * SLOT_BYTES); }
   __device__ __forceinline__ float* slot_v(int s) const {
     return reinterpret_cast<float*>(base + (DBUF ? s : 0) * SLOT_BYTES + CAP * BLK * (int)sizeof(T));
@@ -504,7 +507,16 @@ struct WPipe {
       pend_n = nblk;
       pendv = gv;
       pendv_n = nvec;
+      pend2 = nullptr;
+      pend2_n = 0;
     }
+  }
+  // single slot only: after issue(g, nblk), a second run g2 of n2 blocks lands at block nblk of the
+  // same stage (a stage that reads two separate runs of a blob without fetching what lies between)
+  __device__ __forceinline__ void issue2(const T* g2, int n2) {
+    static_assert(!DBUF, "issue2 is the single-slot pipe's");
+    pend2 = g2;
+    pend2_n = n2;
   }
   __device__ __forceinline__ const T* next() {
     if constexpr (DBUF) {
@@ -514,6 +526,7 @@ struct WPipe {
     } else {
       __syncthreads();
       dma_blocks<NW>(slot_w(0), pend, pend_n);
+      if (pend2_n > 0) dma_blocks<NW>(slot_w(0) + pend_n * BLK, pend2, pend2_n);
       if (pendv) dma_vec<NW>(slot_v(0), pendv, pendv_n / 128);
       lds_dma_wait();
       __syncthreads();

@@ -433,6 +433,10 @@ __device__ __forceinline__ void edge_x32_tile(const EdgeArgs& a, ST& st, int e, 
                                               const u16* wc2) {
   constexpr bool FINAL = MODE == 1;
   static_assert(!Z0 || (GC && !FINAL), "the z0 form is the non-final DI_GRAPH_GEO_REF layer 0");
+  // the lane half is opaque per tile: the bf16 rows' 16-B accesses and the fp32 rows share the byte
+  // offset 16 h, and the compiler otherwise keeps (array base + 16 h) of every array in a register
+  // pair across the block's tile loop -- past the 240 cap in the <0, true, false> form (scratch)
+  asm volatile("" : "+v"(h));
   const u16* f_row = reinterpret_cast<const u16*>(a.f_in) + (int64_t)e * HID;
   const u16* qkv = reinterpret_cast<const u16*>(a.qkv);
 
@@ -497,6 +501,7 @@ __device__ __forceinline__ void edge_x32_tile(const EdgeArgs& a, ST& st, int e, 
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
         asm volatile("" ::: "memory");
+        xn.unswz_blk(b);  // no settle for the gathered row: block by block at its use, as its waits
         floatx16 dg = {};
         dg = mfma32(afrag(w, 2 * b, lane), gop.f[0], dg);
         dg = mfma32(afrag(w, 2 * b + 1, lane), gop.f[1], dg);
@@ -634,14 +639,19 @@ __device__ __forceinline__ void edge_x32_tile(const EdgeArgs& a, ST& st, int e, 
   }
   if (valid && h == 0 && a.alpha_out != nullptr) st4(a.alpha_out + (int64_t)e * 4, al);
   if (!GC && fold) fold_loads();
+  // the general path's V row has no settle(): its layout is restored at the fold, its first use
+  auto attn_fold = [&] {
+    if (!GC) vr.unswz();
+    edge_attn_fold(a, e, valid, lane, h, al, dn, vr, ip);
+  };
   if constexpr (FINAL) {
-    if (fold) edge_attn_fold(a, e, valid, lane, h, al, dn, vr, ip);
+    if (fold) attn_fold();
   } else {
     // ---- edge output: e = in + O_e(e_out); e = e + FFN(BN2e(e)) (:697-724)
     P32<8> pop;
     make_op32(pop, p);
     pin(pop);
-    if (fold) edge_attn_fold(a, e, valid, lane, h, al, dn, vr, ip);  // p is packed: room for the scan
+    if (fold) attn_fold();  // p is packed: room for the scan
     if constexpr (!Z0) fr.load(f_row, h);                    // O_edge: re-read
     w = st.next([&] { if constexpr (!Z0) settle(fr); });  // O_edge_feats
     X32<4> e1;
@@ -678,7 +688,7 @@ __device__ __forceinline__ void edge_x32_tile(const EdgeArgs& a, ST& st, int e, 
       mma32<4, 8>(e1, top, w, lane);
       pin(e1);
     }
-    if (valid) store_row32(e1, reinterpret_cast<u16*>(a.f_out) + (int64_t)e * HID, h);
+    store_row32(e1, reinterpret_cast<u16*>(a.f_out) + (int64_t)e * HID, h, valid);
     if constexpr (GC) return;  // the next layer gathers no silu(nbr_linear(F)) rows
     make_op32(eop, e1);
     w = st.next();  // next layer's silu(nbr_linear(.))
@@ -687,7 +697,7 @@ __device__ __forceinline__ void edge_x32_tile(const EdgeArgs& a, ST& st, int e, 
     mma32<4, 8>(fn, eop, w, lane);
 #pragma unroll
     for (int b = 0; b < 4; ++b) silu_blk(fn.v[b]);
-    if (valid) store_row32(fn, reinterpret_cast<u16*>(a.fn_out) + (int64_t)e * HID, h);
+    store_row32(fn, reinterpret_cast<u16*>(a.fn_out) + (int64_t)e * HID, h, valid);
   }
 }
 

@@ -386,20 +386,39 @@ void k_init_x32(InitArgs a, EmbedArgs ea, int embed_blocks) {
     const u16* w = pipe.next();
     if (p == 0) pipe.issue(W + (IE_T0 + 40 * geo_t(0)) * BLK, 40);
     else if (p < NT) pipe.issue(W + (IE_T0 + 40 * geo_t(p)) * BLK, 40);
-    else if (p == NT) pipe.issue(W + IE_GEO1 * BLK, 40);
+    else if (p == NT) {
+      if constexpr (GC) {  // em1, dist1 and amide1 only: dir1 / orient1 (blocks 16-31) are never read
+        pipe.issue(W + IE_GEO1 * BLK, 16);
+        pipe.issue2(W + (IE_GEO1 + 32) * BLK, 8);
+      } else {
+        pipe.issue(W + IE_GEO1 * BLK, 40);
+      }
+    }
     else if (p == NT + 1) pipe.issue(W + IE_C1 * BLK, Z ? 8 : 16);
     else if (with_fn) pipe.issue(W + IE_NBR * BLK, MAT128);
     return w;
   };
+  // block offset of gate t in the gates phase (GC: the three gates fetched, back to back)
+  auto gate_off = [](int t) { return GC ? (t == 0 ? 0 : (t == 1 ? 8 : 16)) : 8 * t; };
   if constexpr (Z) {
     P32<2> zop;
-    init_tile_x32_z<GC>(acc, gop, a.wvec, lane, h, wt, [](int t) { return 8 * t; }, zop);
+    init_tile_x32_z<GC>(acc, gop, a.wvec, lane, h, wt, gate_off, zop);
     if (valid) store_z0(zop, reinterpret_cast<u16*>(a.f_out), e, h);
     return;
   }
+  // The F / Fn stores take the lane half and the row predicate from a lane id read afresh
+  // (v_mbcnt): held live from the top of the kernel for the 16-B stores they cost the registers the
+  // 160 cap does not have (scratch)
+  auto store_f = [&](const X32<4>& t, void* out) {
+    int l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    asm volatile("" : "+v"(l));
+    const int rr = ((int)blockIdx.x - embed_blocks) * InitX32Geo::ROWS + (threadIdx.x >> 6) * InitX32Geo::ROWS_PER_WAVE +
+                   (l & 31);
+    store_row32(t, reinterpret_cast<u16*>(out) + (int64_t)e * HID, l >> 5, rr < a.Et);
+  };
   X32<4> f;
-  init_tile_x32<GC>(acc, gop, a.wvec, lane, h, wt, [](int t) { return 8 * t; }, f);
-  if (valid) store_row32(f, reinterpret_cast<u16*>(a.f_out) + (int64_t)e * HID, h);
+  init_tile_x32<GC>(acc, gop, a.wvec, lane, h, wt, gate_off, f);
+  store_f(f, a.f_out);
   if (!with_fn) return;
   // layer-0 silu(nbr_linear(F)), applied once per edge and gathered by the conformation module
   const u16* w = pipe.next();
@@ -410,7 +429,7 @@ void k_init_x32(InitArgs a, EmbedArgs ea, int embed_blocks) {
   mma32<4, 8>(fn, fop, w, lane);
 #pragma unroll
   for (int b = 0; b < 4; ++b) silu_blk(fn.v[b]);
-  if (valid) store_row32(fn, reinterpret_cast<u16*>(a.fn_out) + (int64_t)e * HID, h);
+  store_f(fn, a.fn_out);
 }
 
 // resident weights (DI_GRAPH_GEO_REF, no Fn): the path's 128 blocks loaded once per CU into LDS
@@ -464,7 +483,7 @@ void k_init_res_x32(InitArgs a, int ntiles) {
     }
     X32<4> f;
     init_tile_x32<true>(acc, gop, a.wvec, lane, h, wt, gate_off, f);
-    if (valid) store_row32(f, reinterpret_cast<u16*>(a.f_out) + (int64_t)e * HID, h);
+    store_row32(f, reinterpret_cast<u16*>(a.f_out) + (int64_t)e * HID, h, valid);
   }
 }
 

@@ -38,16 +38,65 @@ template <int NS>
 struct P32 {
   bf16x8 f[NS];
 };
+// Row access width of R32::load / store_row32. 1 (the product build): 16 B per lane; 0 (the `rows8`
+// variant of tools/build_variants.py, kept as the reference of tests/test_gpu_wide_rows.py): the 8-B
+// accumulator-quad accesses. Same bytes at the same addresses either way, and no alignment beyond
+// the 8 B of the narrow form.
+#ifndef DI_ROW_WIDE
+#define DI_ROW_WIDE 1
+#endif
+
+// 16 B of a row that is only known to be 8-B aligned (global memory takes the access unaligned)
+typedef uint32_t row16 __attribute__((ext_vector_type(4), aligned(8)));
+
+// {a, b} -> {a of lane half 0 | b of lane half 0, a of lane half 1 | b of lane half 1} over the
+// lanes' (low | high) halves: v_permlane32_swap exchanges a's high 32 lanes with b's low 32
+__device__ __forceinline__ void swap32(uint32_t& a, uint32_t& b) {
+  const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+  a = r[0];
+  b = r[1];
+}
+
 // a row of NB*32 bf16 features in its storage format, laid out as the accumulator quads:
 // u[4b + q] = features 32 b + 8 q + 4 h .. +3 (8 bytes)
+// load() fetches the row 16 B per lane: load j of lane (row, h) takes bytes 32 j + 16 h .. +15 into
+// u[2j], u[2j+1], i.e. quad 2j + h of BOTH lane halves. Until unswz() the registers hold that
+// "wide" order; unswz() (two v_permlane32_swap per load: .x <-> .x, .y <-> .y of the two 8-B
+// pieces between the row's two lanes) leaves the layout above. It reads the loaded registers, so it
+// belongs where the data has landed -- settle(), or just before the row's first use -- never at the
+// load site, and runs exactly once per load. With DI_ROW_WIDE=0 load() is the 8-B form and unswz()
+// is empty.
 template <int NB>
 struct R32 {
   uint2 u[4 * NB];
   __device__ __forceinline__ void load(const u16* row, int h) {
+#if DI_ROW_WIDE
+#pragma unroll
+    for (int j = 0; j < 2 * NB; ++j) {
+      const row16 w = *reinterpret_cast<const row16*>(row + 16 * j + 8 * h);
+      u[2 * j] = (uint2){w[0], w[1]};
+      u[2 * j + 1] = (uint2){w[2], w[3]};
+    }
+#else
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
       for (int q = 0; q < 4; ++q) u[4 * b + q] = *reinterpret_cast<const uint2*>(row + 32 * b + 8 * q + 4 * h);
+#endif
+  }
+  // block b (loads 2b, 2b+1) / the whole row from the wide order to the layout above
+  __device__ __forceinline__ void unswz_blk(int b) {
+#if DI_ROW_WIDE
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      swap32(u[4 * b + 2 * t].x, u[4 * b + 2 * t + 1].x);
+      swap32(u[4 * b + 2 * t].y, u[4 * b + 2 * t + 1].y);
+    }
+#endif
+  }
+  __device__ __forceinline__ void unswz() {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) unswz_blk(b);
   }
 };
 
@@ -111,15 +160,33 @@ __device__ __forceinline__ void to_x32(X32<NB>& a, const R32<NB>& r) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) set_quad(a.v[b], q, unpack4(r.u[4 * b + q]));
 }
+// the row's bf16 bytes, written by the lanes with `valid`; 16 B per lane: quads 2j, 2j+1 swapped
+// between the row's two lanes (the mirror image of R32::unswz), then lane (row, h) stores quad
+// 2j + h of both halves at bytes 32 j + 16 h. Called by the whole wave: the swaps run with every
+// lane active, only the stores are predicated.
 template <int NB>
-__device__ __forceinline__ void store_row32(const X32<NB>& a, u16* row, int h) {
+__device__ __forceinline__ void store_row32(const X32<NB>& a, u16* row, int h, bool valid) {
+#if DI_ROW_WIDE
+#pragma unroll
+  for (int j = 0; j < 2 * NB; ++j) {
+    const floatx4 x = quad(a.v[j / 2], 2 * (j % 2)), y = quad(a.v[j / 2], 2 * (j % 2) + 1);
+    uint32_t x0 = pack_bf16x2(x[0], x[1]), x1 = pack_bf16x2(x[2], x[3]);
+    uint32_t y0 = pack_bf16x2(y[0], y[1]), y1 = pack_bf16x2(y[2], y[3]);
+    swap32(x0, y0);
+    swap32(x1, y1);
+    if (valid) *reinterpret_cast<row16*>(row + 16 * j + 8 * h) = (row16){x0, x1, y0, y1};
+    __builtin_amdgcn_sched_barrier(0);  // one packed 16 B live at a time (k_init_x32 sits at its register cap)
+  }
+#else
 #pragma unroll
   for (int b = 0; b < NB; ++b)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const floatx4 x = quad(a.v[b], q);
-      *reinterpret_cast<uint2*>(row + 32 * b + 8 * q + 4 * h) = (uint2){pack_bf16x2(x[0], x[1]), pack_bf16x2(x[2], x[3])};
+      if (valid)
+        *reinterpret_cast<uint2*>(row + 32 * b + 8 * q + 4 * h) = (uint2){pack_bf16x2(x[0], x[1]), pack_bf16x2(x[2], x[3])};
     }
+#endif
 }
 
 // k-steps 2b, 2b+1 of an operand from block b of an accumulator
@@ -163,10 +230,12 @@ __device__ __forceinline__ void pin(P32<NS>& o) {
 #pragma unroll
   for (int s = 0; s < NS; ++s) asm volatile("" : "+v"(o.f[s]));
 }
+// the row's loads have landed (the caller's vmcnt wait): pin the wait here, then restore the layout
 template <int NB>
-__device__ __forceinline__ void settle(const R32<NB>& r) {
+__device__ __forceinline__ void settle(R32<NB>& r) {
 #pragma unroll
   for (int i = 0; i < 4 * NB; ++i) asm volatile("" ::"v"(r.u[i].x), "v"(r.u[i].y));
+  r.unswz();
 }
 
 __device__ __forceinline__ void silu2_blk(floatx16& v) {

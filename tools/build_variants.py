@@ -15,6 +15,11 @@ VARIANTS = {
     "node2": ["DI_NODE_NW=2"],
     # fp32 SiLU as libm expf + IEEE division (csrc/common.h DI_F32_FAST_SILU; the round-2 default)
     "f32exact": ["DI_F32_FAST_SILU=0"],
+    # the 32x32 bf16 edge / InitEdge kernels' rows as 8-B accesses per lane, 16 per 256-B row, in place
+    # of the product's eight 16-B ones (csrc/mfma32.h DI_ROW_WIDE: R32::load / unswz, store_row32). Same
+    # bytes, same addresses: tests/test_gpu_wide_rows.py holds the two builds bit-identical, and it is
+    # the A/B arm of profiles/wide_rows_ab.txt
+    "rows8": ["DI_ROW_WIDE=0"],
 }
 # Rejected experiments are recorded in DESIGN.md §8 and removed from the sources; timing diagnostics
 # that need patched kernels are built from patched source copies by tools/diag/ (never -D knobs in csrc).

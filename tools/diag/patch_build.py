@@ -34,17 +34,33 @@ DIAGS = {
     "initnopos": [("geot_init.hip", "  init_acc_x32(acc, a, a.node_pos[a.src[e]], a.node_pos[a.dst[e]], h);\n  const bool with_fn",
                    "  zero(acc);\n  const bool with_fn", 1)],
     # InitEdge without its F row stores (kept alive by a never-true condition)
-    "initnostore": [("geot_init.hip", "  if (valid) store_row32(f, reinterpret_cast<u16*>(a.f_out) + (int64_t)e * HID, h);\n  if (!with_fn) return;",
-                     "  if (valid && f.v[0][0] == 1.2345e30f) store_row32(f, reinterpret_cast<u16*>(a.f_out) + (int64_t)e * HID, h);\n  if (!with_fn) return;", 1)],
+    "initnostore": [("geot_init.hip", "  store_f(f, a.f_out);\n  if (!with_fn) return;",
+                     "  if (f.v[0][0] == 1.2345e30f) store_f(f, a.f_out);\n  if (!with_fn) return;", 1)],
     # InitEdge's weight phases all DMA'd from the blob's first blocks (L2-resident; wrong weights)
     "initw0": [("geot_init.hip", """    if (p == 0) pipe.issue(W + (IE_T0 + 40 * geo_t(0)) * BLK, 40);
     else if (p < NT) pipe.issue(W + (IE_T0 + 40 * geo_t(p)) * BLK, 40);
-    else if (p == NT) pipe.issue(W + IE_GEO1 * BLK, 40);
+    else if (p == NT) {
+      if constexpr (GC) {  // em1, dist1 and amide1 only: dir1 / orient1 (blocks 16-31) are never read
+        pipe.issue(W + IE_GEO1 * BLK, 16);
+        pipe.issue2(W + (IE_GEO1 + 32) * BLK, 8);
+      } else {
+        pipe.issue(W + IE_GEO1 * BLK, 40);
+      }
+    }
     else if (p == NT + 1) pipe.issue(W + IE_C1 * BLK, Z ? 8 : 16);""", """    if (p == 0) pipe.issue(W, 40);
     else if (p < NT) pipe.issue(W, 40);
-    else if (p == NT) pipe.issue(W, 40);
+    else if (p == NT) pipe.issue(W, GC ? 24 : 40);
     else if (p == NT + 1) pipe.issue(W, Z ? 8 : 16);""", 1)],
     # A/B variants with CORRECT results (timing comparisons of one-line changes, never shipped):
+    # k_init_x32<true, *>'s gates phase fetching all 40 blocks of IE_GEO1 (dir1 / orient1 unread), as
+    # before the 16 + 8 fetch: the arm of profiles/wide_rows_ab.txt that separates that change
+    "gate40": [("geot_init.hip", """      if constexpr (GC) {  // em1, dist1 and amide1 only: dir1 / orient1 (blocks 16-31) are never read
+        pipe.issue(W + IE_GEO1 * BLK, 16);
+        pipe.issue2(W + (IE_GEO1 + 32) * BLK, 8);
+      } else {""", """      if constexpr (false) {
+      } else {""", 1),
+               ("geot_init.hip", "  auto gate_off = [](int t) { return GC ? (t == 0 ? 0 : (t == 1 ? 8 : 16)) : 8 * t; };",
+                "  auto gate_off = [](int t) { return 8 * t; };", 1)],
     # the edge ring issuing each weight stage three stages ahead (two in the product)
     "ahead3": [("geot_edge.hip", "constexpr int RING_NW = 8, RING_SLOTS = 4, RING_AHEAD = 2;",
                 "constexpr int RING_NW = 8, RING_SLOTS = 4, RING_AHEAD = 3;", 1)],
