@@ -55,6 +55,12 @@ class DiRankMetrics(ctypes.Structure):
 
 DI_RANK_MAX_K = 4096
 
+
+class DiAucMetrics(ctypes.Structure):
+    _fields_ = [("num_pos", ctypes.c_int64), ("num_neg", ctypes.c_int64), ("num_nan", ctypes.c_int64),
+                ("pos_distinct", ctypes.c_int64), ("u2", ctypes.c_uint64), ("auroc", ctypes.c_double),
+                ("auprc", ctypes.c_double), ("overflow", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
 # pair-queue words (include/deepinteract_amd.h, di_pair_queue_bytes)
 PQ_READY, PQ_ERROR, PQ_GAVE_UP, PQ_SBYTES, PQ_HBYTES = 0, 32, 33, 40, 42
 
@@ -101,6 +107,8 @@ _SIGS = {
     "di_channel_mean": ([_I, _P, _I, ctypes.c_int64, _P, _P, _P, _P], ctypes.c_int),
     "di_contact_rank_work_bytes": ([ctypes.c_int64, _I], ctypes.c_int64),
     "di_contact_rank": ([_I, _P, _I, _I, _I, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
+    "di_contact_auc_work_bytes": ([ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),
+    "di_contact_auc": ([_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P], ctypes.c_int),
     "di_knn_topk": ([_I, _P, _P, _I, _I, _P, _P, _P], ctypes.c_int),
     "di_geo_feats": ([ctypes.POINTER(DiGeoArgs), _P], ctypes.c_int),
     "di_build_nbr_ids": ([_I, _P, _P, _P, ctypes.c_uint64, _P, _P], ctypes.c_int),

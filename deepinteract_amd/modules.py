@@ -24,7 +24,7 @@ from .config import GeoTConfig, NODE_COUNT_LIMIT, RESIDUE_COUNT_LIMIT
 from .engine import GeoTEngine, HeadPrologueOp, PairTensorOp, gpu_device
 from .graph import GraphBatch, ResidueGraph, batch as batch_graphs, unbatch
 from .head import HeadNormOps, ResNet2DInputWithOptAttention, contact_probs
-from .ranking import ContactRankOp, labels_from_examples, topk_metrics
+from .ranking import ContactAucOp, ContactRankOp, confusion_metrics, labels_from_examples, topk_metrics
 
 
 def _identity_embedding_sd(sd, cfg: GeoTConfig):
@@ -126,6 +126,7 @@ class LitGINI(nn.Module):
         self._prologue_w = None  # fp32 host copies of conv2d_1 / inorm_1 (fused head prologue)
         self._dev_ops = None     # (device, GeoTEngine, PairTensorOp, HeadPrologueOp | None)
         self._rank_op = None     # ContactRankOp on the model's device
+        self._auc_op = None      # ContactAucOp on the model's device
 
     def load_reference_state_dict(self, sd):
         """Reference-keyed LitGINI state dict. The head loads into this nn.Module; the GeoT
@@ -272,6 +273,12 @@ class LitGINI(nn.Module):
             self._rank_op = ContactRankOp(dev)
         return self._rank_op
 
+    def _auc(self):
+        dev = self.engine.device
+        if self._auc_op is None or self._auc_op.device != dev:
+            self._auc_op = ContactAucOp(dev)
+        return self._auc_op
+
     def predict_contacts(self, gb: GraphBatch, pairs, k=None):
         """predict_batch with each complex's ranked contacts: (logits, [ranking.ContactRanking]) --
         the probability map, the k best contacts (default k = min(L1, L2)) as flat ids, (i, j) pairs
@@ -290,10 +297,12 @@ class LitGINI(nn.Module):
         Returns the reference's keys this build computes: loss (mean cross-entropy), top_10_prec,
         top_l_by_10_prec, top_l_by_5_prec, top_l_recall, top_l_by_2_recall, top_l_by_5_recall
         (l = min(L1, L2); float('nan') where the reference would divide by zero, ranking.topk_metrics),
-        test_preds / test_preds_rounded / test_labels as [L1, L2] numpy arrays, target, and
-        confusion = {tp, fp, fn, tn} at pos_prob_threshold. Out of scope: torchmetrics' test_acc /
-        test_prec / test_recall / test_f1 / test_auroc / test_auprc (the confusion counts are what the
-        first four are computed from)."""
+        test_preds / test_preds_rounded / test_labels as [L1, L2] numpy arrays, target,
+        confusion = {tp, fp, fn, tn} at pos_prob_threshold, test_auroc / test_auprc (the first complex's
+        exact class-1 AUROC and average precision of test_preds against test_labels,
+        ranking.ContactAucOp; float('nan') when a class is empty or a score is NaN), and test_acc /
+        test_prec / test_recall / test_f1 from the summed confusion counts (torchmetrics' class-1
+        definitions restated, ranking.confusion_metrics)."""
         import os
         graph1, graph2, examples_list, filepaths = batch[0], batch[1], batch[2], batch[3]
         logits_list = self.shared_step(graph1, graph2)
@@ -307,6 +316,7 @@ class LitGINI(nn.Module):
             results.append((rank(logits.contiguous(), k=min(l1, l2), labels=labels,
                                  threshold=self.pos_prob_threshold), labels, l1, l2))
         r0, labels0, l1, l2 = results[0]
+        auc = self._auc()(r0.probs, labels0)   # the map the ranking judged
         n_all = sum(a * b for _, _, a, b in results)
         confusion = {f: sum(getattr(r, f) for r, _, _, _ in results) for f in ("tp", "fp", "fn", "tn")}
         out = {"loss": sum(r.ce_sum for r, _, _, _ in results) / n_all}
@@ -317,6 +327,8 @@ class LitGINI(nn.Module):
         out["test_labels"] = labels0.view(l1, l2).float().cpu().numpy()
         out["target"] = str(filepaths[0]).split(os.sep)[-1][:4]
         out["confusion"] = confusion
+        out["test_auroc"], out["test_auprc"] = auc.auroc, auc.auprc
+        out.update(confusion_metrics(**confusion))
         return out
 
 

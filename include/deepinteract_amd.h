@@ -33,6 +33,8 @@
  *   di_build_nbr_ids_torch  the same, bit-exact with torch.randperm  deepinteract_utils.py:539-546
  *   di_contact_rank  LitGINI.test_step's softmax, ranking and counters deepinteract_modules.py:2018-2101,
  *                                                                    deepinteract_utils.py:977-995
+ *   di_contact_auc   test_step's exact per-complex test_auroc / test_auprc (class 1)
+ *                                                                    deepinteract_modules.py:2018-2101
  *
  * Module-at-a-time entry points (deepinteract_amd/layers.py; same math as the fused kernels):
  *   di_conformation   ConformationModule.forward                      deepinteract_modules.py:373-455
@@ -376,6 +378,38 @@ int di_contact_rank(int32_t dtype, const void* logits, int32_t l1, int32_t l2, i
                     const uint8_t* labels, float threshold, float* probs, int32_t* top_ids,
                     float* top_scores, int32_t* top_hits, di_rank_metrics* metrics,
                     void* work, void* stream);
+
+/* ---- exact per-complex AUROC / AUPRC (an addition to ABI 8) ---------------------------------
+ * test_auroc / test_auprc of LitGINI.test_step (deepinteract_modules.py:2018-2101) for class 1 of one
+ * complex: roc_curve + trapezoid and average precision over the distinct thresholds (torchmetrics'
+ * exact mode, scikit-learn), without sorting the map. probs [n] fp32 in [0, 1] or NaN, 16-B aligned
+ * (the map di_contact_rank stored); labels [n] uint8, non-zero = positive.
+ * key = bits of p (monotone for p >= 0). P = num_pos, N = num_neg. Positives grouped by distinct key,
+ * descending: groups g = 0 .. U-1 with counts c_g, TP_g = c_0 + .. + c_g, FP_g = negatives with
+ * key >= key_g.
+ *   u2     sum over (pos, neg) pairs of 2 [p_pos > p_neg] + [p_pos == p_neg], an exact integer
+ *   auroc  u2 / (2 P N), one correctly rounded fp64 quotient of the exact integers
+ *   auprc  (1 / P) sum_g c_g TP_g / (TP_g + FP_g), terms in fp64, summed in an order that is a
+ *          function of U alone
+ * num_pos, num_neg (by label) and num_nan (NaN scores of either label) are always filled. With
+ * P = 0, N = 0 or num_nan > 0 both figures are NaN and u2 = pos_distinct = 0. overflow = 1 when
+ * num_pos > max_pos (the positives' buffer, never written past): then too nothing but the three
+ * counts is valid and both figures are NaN; call again with max_pos >= num_pos.
+ * work: di_contact_auc_work_bytes bytes, 16-B aligned; cleared in-stream by the call, so calls that
+ * share it need only stream order. The call is asynchronous on `stream` and allocates nothing; out
+ * is device memory. Outputs are bit-reproducible from run to run (integer atomics only).
+ * DI_EINVAL: n < 1, max_pos < 1, max_pos > n, a NULL pointer, probs or work not 16-B aligned.
+ * DI_ERANGE: n >= 2^29. di_contact_auc_work_bytes returns the same -1 / -2. */
+typedef struct {
+  int64_t num_pos, num_neg, num_nan;
+  int64_t pos_distinct;
+  uint64_t u2;
+  double auroc, auprc;
+  int32_t overflow, pad;
+} di_auc_metrics;
+int64_t di_contact_auc_work_bytes(int64_t n, int64_t max_pos);
+int di_contact_auc(const float* probs, const uint8_t* labels, int64_t n, int64_t max_pos,
+                   di_auc_metrics* out, void* work, void* stream);
 
 /* ---- graph builder ----------------------------------------------------------------------- */
 /* Cα kNN per chain: idx_out [Nt,k] chain-local neighbour ids (ascending squared distance,
