@@ -61,6 +61,23 @@ class DiAucMetrics(ctypes.Structure):
                 ("pos_distinct", ctypes.c_int64), ("u2", ctypes.c_uint64), ("auroc", ctypes.c_double),
                 ("auprc", ctypes.c_double), ("overflow", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
+
+DI_BATCH_MAX = 1024
+
+
+class DiRankItem(ctypes.Structure):
+    _fields_ = [("logits", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("probs", ctypes.c_void_p),
+                ("top_ids", ctypes.c_void_p), ("top_scores", ctypes.c_void_p), ("top_hits", ctypes.c_void_p),
+                ("metrics", ctypes.c_void_p), ("hdr_off", ctypes.c_int64), ("work_off", ctypes.c_int64),
+                ("l1", ctypes.c_int32), ("l2", ctypes.c_int32), ("k", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class DiAucItem(ctypes.Structure):
+    _fields_ = [("probs", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("n", ctypes.c_int64), ("max_pos", ctypes.c_int64), ("hdr_off", ctypes.c_int64),
+                ("work_off", ctypes.c_int64)]
+
+
 # pair-queue words (include/deepinteract_amd.h, di_pair_queue_bytes)
 PQ_READY, PQ_ERROR, PQ_GAVE_UP, PQ_SBYTES, PQ_HBYTES = 0, 32, 33, 40, 42
 
@@ -109,6 +126,10 @@ _SIGS = {
     "di_contact_rank": ([_I, _P, _I, _I, _I, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
     "di_contact_auc_work_bytes": ([ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),
     "di_contact_auc": ([_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P], ctypes.c_int),
+    "di_contact_rank_batch_work_bytes": ([_P, _I], ctypes.c_int64),
+    "di_contact_rank_batch": ([_I, _P, _P, _I, ctypes.c_float, _P, _P], ctypes.c_int),
+    "di_contact_auc_batch_work_bytes": ([_P, _I], ctypes.c_int64),
+    "di_contact_auc_batch": ([_P, _P, _I, _P, _P], ctypes.c_int),
     "di_knn_topk": ([_I, _P, _P, _I, _I, _P, _P, _P], ctypes.c_int),
     "di_geo_feats": ([ctypes.POINTER(DiGeoArgs), _P], ctypes.c_int),
     "di_build_nbr_ids": ([_I, _P, _P, _P, ctypes.c_uint64, _P, _P], ctypes.c_int),

@@ -37,6 +37,8 @@
 //                   u2 and of the fp64 sum (group order per thread, a fixed tree per block)
 //   k_auc_finish    one block: the tiles' shares in a fixed order, the record
 // Algorithmic bytes per element: 2 x (4 + 1) read = 10 B; the sort touches O(P) words.
+// di_contact_auc_batch runs the same sequence once for many complexes (grid y = complex; "the batch"
+// below): the same kernel bodies on the same per-complex geometry, so the same bits per complex.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -85,7 +87,10 @@ struct AucWork {
   int64_t clear_bytes, bytes;
 };
 
-static AucWork auc_work(void* work, int64_t max_pos) {
+// work: the cleared part (header, eq, gap); rest: everything else (directly behind it in a single call's
+// workspace; in a batch the cleared parts of all complexes are contiguous, so that one memset clears
+// them). A function of max_pos alone, on host and device.
+__host__ __device__ static inline AucWork auc_work(void* work, void* rest, int64_t max_pos) {
   AucWork w;
   w.a = (max_pos + 1 + 3) / 4 * 4;
   int64_t nws = (max_pos + AU_SORT_KEYS_PER_WAVE - 1) / AU_SORT_KEYS_PER_WAVE;
@@ -101,7 +106,7 @@ static AucWork auc_work(void* work, int64_t max_pos) {
   w.hdr = reinterpret_cast<AucHdr*>(p);
   w.eq = reinterpret_cast<uint32_t*>(p + sizeof(AucHdr));
   w.gap = w.eq + w.a;
-  w.keys_a = w.gap + w.a;
+  w.keys_a = reinterpret_cast<uint32_t*>(rest);
   w.keys_b = w.keys_a + w.a;
   w.uk = w.keys_b + w.a;
   w.upos = w.uk + w.a;
@@ -119,7 +124,7 @@ static AucWork auc_work(void* work, int64_t max_pos) {
 struct AucGeo {
   int nv, nb, per;
 };
-static AucGeo auc_geo(int64_t n) {
+__host__ __device__ static inline AucGeo auc_geo(int64_t n) {
   AucGeo g;
   g.nv = (int)((n + 3) / 4);
   const int64_t want = (g.nv + AU_THREADS * 4 - 1) / (AU_THREADS * 4);
@@ -175,15 +180,18 @@ __device__ __forceinline__ uint32_t auc_excl_scan(uint32_t v, uint32_t* s) {
 }
 
 // ---------------------------------------------------------------- pass 1: counts, positives
-__global__ __launch_bounds__(AU_THREADS) void k_auc_collect(const float* __restrict__ probs,
-                                                            const uint8_t* __restrict__ labels, int n, int nv, int per,
-                                                            uint32_t max_pos, AucHdr* __restrict__ hdr,
-                                                            uint32_t* __restrict__ keys) {
+// Every stage is a __device__ body behind two thin entry points: k_x for one complex and k_x_b for a
+// batch, where the grid's y index names the complex (see "the batch" below). bx is the block's index
+// inside its complex.
+__device__ __forceinline__ void auc_collect_body(const int bx, const float* __restrict__ probs,
+                                                 const uint8_t* __restrict__ labels, int n, int nv, int per,
+                                                 uint32_t max_pos, AucHdr* __restrict__ hdr,
+                                                 uint32_t* __restrict__ keys) {
   __shared__ uint32_t stage_all[AU_WAVES][AU_STAGE];
   __shared__ uint32_t red[3][AU_WAVES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   volatile uint32_t* stage = stage_all[wave];  // written and read back by this wave only, in program order
-  const int lo = (blockIdx.x * AU_WAVES + wave) * per;
+  const int lo = (bx * AU_WAVES + wave) * per;
   const int hi = lo + per < nv ? lo + per : nv;
   const unsigned long long below = (1ull << lane) - 1ull;
   uint32_t c_pos = 0, c_neg = 0, c_nan = 0;
@@ -245,9 +253,9 @@ __global__ __launch_bounds__(AU_THREADS) void k_auc_collect(const float* __restr
 }
 
 // ---------------------------------------------------------------- P <= AU_SMALL: one block
-__global__ __launch_bounds__(AU_ONE_THREADS) void k_auc_small(AucHdr* __restrict__ hdr, uint32_t max_pos,
-                                                              const uint32_t* __restrict__ keys,
-                                                              uint32_t* __restrict__ uk, uint32_t* __restrict__ upos) {
+__device__ __forceinline__ void auc_small_body(AucHdr* __restrict__ hdr, uint32_t max_pos,
+                                               const uint32_t* __restrict__ keys, uint32_t* __restrict__ uk,
+                                               uint32_t* __restrict__ upos) {
   static_assert(AU_SMALL == 4 * AU_ONE_THREADS, "4 ranks per thread");
   __shared__ uint32_t s[AU_SMALL];
   __shared__ uint32_t sc[16];
@@ -305,12 +313,12 @@ __device__ __forceinline__ bool auc_sorted_by_block(const AucHdr* __restrict__ h
   return auc_idle(hdr, max_pos) || hdr->pos <= (unsigned long long)AU_SMALL;
 }
 
-__global__ __launch_bounds__(AU_THREADS) void k_auc_rhist(const AucHdr* __restrict__ hdr, uint32_t max_pos, int nws,
-                                                          int shift, const uint32_t* __restrict__ src,
-                                                          uint32_t* __restrict__ whist) {
+__device__ __forceinline__ void auc_rhist_body(const int bx, const AucHdr* __restrict__ hdr, uint32_t max_pos, int nws,
+                                               int shift, const uint32_t* __restrict__ src,
+                                               uint32_t* __restrict__ whist) {
   __shared__ uint32_t h[AU_WAVES][256];
   if (auc_sorted_by_block(hdr, max_pos)) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, w = blockIdx.x * AU_WAVES + wave;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, w = bx * AU_WAVES + wave;
   for (int i = lane; i < 256; i += 64) h[wave][i] = 0;
   __syncthreads();
   const AucSlice sl = auc_slice((uint32_t)hdr->pos, nws, w);
@@ -321,12 +329,12 @@ __global__ __launch_bounds__(AU_THREADS) void k_auc_rhist(const AucHdr* __restri
 
 // block d: exclusive prefix sum of digit d's counts over the waves (a coalesced row of the table), and
 // the digit's total
-__global__ __launch_bounds__(AU_THREADS) void k_auc_rscan(const AucHdr* __restrict__ hdr, uint32_t max_pos, int nws,
-                                                          uint32_t* __restrict__ whist, uint32_t* __restrict__ dtot) {
+__device__ __forceinline__ void auc_rscan_body(const int bx, const AucHdr* __restrict__ hdr, uint32_t max_pos, int nws,
+                                               uint32_t* __restrict__ whist, uint32_t* __restrict__ dtot) {
   static_assert(AU_SORT_MAX_WAVES <= 4 * AU_THREADS, "4 waves' counts per thread");
   __shared__ uint32_t sc[16];
   if (auc_sorted_by_block(hdr, max_pos)) return;
-  uint32_t* __restrict__ row = whist + (size_t)blockIdx.x * nws;
+  uint32_t* __restrict__ row = whist + (size_t)bx * nws;
   const int i0 = 4 * threadIdx.x;
   uint32_t c[4], sum = 0;
 #pragma unroll
@@ -337,19 +345,18 @@ __global__ __launch_bounds__(AU_THREADS) void k_auc_rscan(const AucHdr* __restri
     if (i0 + j < nws) row[i0 + j] = run;
     run += c[j];
   }
-  if (threadIdx.x == AU_THREADS - 1) dtot[blockIdx.x] = run;
+  if (threadIdx.x == AU_THREADS - 1) dtot[bx] = run;
 }
 
-__global__ __launch_bounds__(AU_THREADS) void k_auc_rscatter(const AucHdr* __restrict__ hdr, uint32_t max_pos, int nws,
-                                                             int shift, const uint32_t* __restrict__ src,
-                                                             const uint32_t* __restrict__ whist,
-                                                             const uint32_t* __restrict__ dtot,
-                                                             uint32_t* __restrict__ dst) {
+__device__ __forceinline__ void auc_rscatter_body(const int bx, const AucHdr* __restrict__ hdr, uint32_t max_pos,
+                                                  int nws, int shift, const uint32_t* __restrict__ src,
+                                                  const uint32_t* __restrict__ whist,
+                                                  const uint32_t* __restrict__ dtot, uint32_t* __restrict__ dst) {
   static_assert(AU_THREADS == 256, "one thread per digit");
   __shared__ uint32_t off_all[AU_WAVES][256];
   __shared__ uint32_t dbase[256], sc[16];
   if (auc_sorted_by_block(hdr, max_pos)) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, w = blockIdx.x * AU_WAVES + wave;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, w = bx * AU_WAVES + wave;
   dbase[threadIdx.x] = auc_excl_scan(dtot[threadIdx.x], sc);  // the keys with a smaller digit
   __syncthreads();
   volatile uint32_t* off = off_all[wave];  // this wave's running offsets, read and advanced in program order
@@ -379,11 +386,10 @@ __global__ __launch_bounds__(AU_THREADS) void k_auc_rscatter(const AucHdr* __res
 }
 
 // head flags of the sorted keys: how many groups start in each wave's slice
-__global__ __launch_bounds__(AU_THREADS) void k_auc_heads(const AucHdr* __restrict__ hdr, uint32_t max_pos, int nws,
-                                                          const uint32_t* __restrict__ keys,
-                                                          uint32_t* __restrict__ wheads) {
+__device__ __forceinline__ void auc_heads_body(const int bx, const AucHdr* __restrict__ hdr, uint32_t max_pos, int nws,
+                                               const uint32_t* __restrict__ keys, uint32_t* __restrict__ wheads) {
   if (auc_sorted_by_block(hdr, max_pos)) return;
-  const int lane = threadIdx.x & 63, w = blockIdx.x * AU_WAVES + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63, w = bx * AU_WAVES + (threadIdx.x >> 6);
   const AucSlice sl = auc_slice((uint32_t)hdr->pos, nws, w);
   uint32_t c = 0;
   for (uint32_t i = sl.lo + lane; i < sl.hi; i += 64) c += i == 0 || keys[i] != keys[i - 1];
@@ -392,14 +398,13 @@ __global__ __launch_bounds__(AU_THREADS) void k_auc_heads(const AucHdr* __restri
   if (lane == 0) wheads[w] = c;
 }
 
-__global__ __launch_bounds__(AU_THREADS) void k_auc_uniq(AucHdr* __restrict__ hdr, uint32_t max_pos, int nws,
-                                                         const uint32_t* __restrict__ keys,
-                                                         const uint32_t* __restrict__ wheads, uint32_t* __restrict__ uk,
-                                                         uint32_t* __restrict__ upos) {
+__device__ __forceinline__ void auc_uniq_body(const int bx, AucHdr* __restrict__ hdr, uint32_t max_pos, int nws,
+                                              const uint32_t* __restrict__ keys, const uint32_t* __restrict__ wheads,
+                                              uint32_t* __restrict__ uk, uint32_t* __restrict__ upos) {
   __shared__ uint32_t red[AU_WAVES];
   if (auc_sorted_by_block(hdr, max_pos)) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int w0 = blockIdx.x * AU_WAVES, w = w0 + wave;
+  const int w0 = bx * AU_WAVES, w = w0 + wave;
   uint32_t g = 0;  // the groups that start in the waves before this block
   for (int i = threadIdx.x; i < w0; i += AU_THREADS) g += wheads[i];
 #pragma unroll
@@ -430,11 +435,11 @@ __global__ __launch_bounds__(AU_THREADS) void k_auc_uniq(AucHdr* __restrict__ hd
 }
 
 // ---------------------------------------------------------------- pass 2: the negatives' bins
-__global__ __launch_bounds__(AU_THREADS) void k_auc_bin(const float* __restrict__ probs,
-                                                        const uint8_t* __restrict__ labels, int n, int nv, int per,
-                                                        uint32_t max_pos, AucHdr* __restrict__ hdr,
-                                                        const uint32_t* __restrict__ uk, uint32_t* __restrict__ eq,
-                                                        uint32_t* __restrict__ gap) {
+__device__ __forceinline__ void auc_bin_body(const int bx, const float* __restrict__ probs,
+                                             const uint8_t* __restrict__ labels, int n, int nv, int per,
+                                             uint32_t max_pos, AucHdr* __restrict__ hdr,
+                                             const uint32_t* __restrict__ uk, uint32_t* __restrict__ eq,
+                                             uint32_t* __restrict__ gap) {
   if (auc_idle(hdr, max_pos)) return;
   const uint32_t U = hdr->U;
   if (U == 0 || U > max_pos) return;  // never: P > 0
@@ -448,7 +453,7 @@ __global__ __launch_bounds__(AU_THREADS) void k_auc_bin(const float* __restrict_
   }
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lo = (blockIdx.x * AU_WAVES + wave) * per;
+  const int lo = (bx * AU_WAVES + wave) * per;
   const int hi = lo + per < nv ? lo + per : nv;
   uint32_t c_tgt = 0, c_teq = 0, c_beq = 0;
   for (int v = lo + lane; v < hi; v += 64) {
@@ -531,14 +536,13 @@ __device__ __forceinline__ AucBins auc_bins(const AucHdr* __restrict__ hdr, cons
 }
 
 // tsum[b] = negatives in the bins of tile b
-__global__ __launch_bounds__(AU_THREADS) void k_auc_tiles(const AucHdr* __restrict__ hdr, uint32_t max_pos,
-                                                          const uint32_t* __restrict__ eq,
-                                                          const uint32_t* __restrict__ gap,
-                                                          uint32_t* __restrict__ tsum) {
+__device__ __forceinline__ void auc_tiles_body(const int bx, const AucHdr* __restrict__ hdr, uint32_t max_pos,
+                                               const uint32_t* __restrict__ eq, const uint32_t* __restrict__ gap,
+                                               uint32_t* __restrict__ tsum) {
   __shared__ uint32_t red[AU_WAVES];
   if (auc_idle(hdr, max_pos)) return;
   const AucBins bins = auc_bins(hdr, eq, gap);
-  const unsigned long long t0 = (unsigned long long)blockIdx.x * AU_TILE;
+  const unsigned long long t0 = (unsigned long long)bx * AU_TILE;
   if (bins.U > max_pos || t0 >= bins.U) return;  // block-uniform
   const uint32_t g0 = (uint32_t)t0 + 4u * threadIdx.x;
   uint32_t sum = 0;
@@ -549,29 +553,27 @@ __global__ __launch_bounds__(AU_THREADS) void k_auc_tiles(const AucHdr* __restri
   for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
   __syncthreads();
-  if (threadIdx.x == 0) tsum[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  if (threadIdx.x == 0) tsum[bx] = red[0] + red[1] + red[2] + red[3];
 }
 
 // FP_g from the tiles before this one and a scan inside it; the tile's share of u2 and of the fp64 sum
-__global__ __launch_bounds__(AU_THREADS) void k_auc_terms(const AucHdr* __restrict__ hdr, uint32_t max_pos,
-                                                          const uint32_t* __restrict__ upos,
-                                                          const uint32_t* __restrict__ eq,
-                                                          const uint32_t* __restrict__ gap,
-                                                          const uint32_t* __restrict__ tsum,
-                                                          unsigned long long* __restrict__ part_u2,
-                                                          double* __restrict__ part_ap) {
+__device__ __forceinline__ void auc_terms_body(const int bx, const AucHdr* __restrict__ hdr, uint32_t max_pos,
+                                               const uint32_t* __restrict__ upos, const uint32_t* __restrict__ eq,
+                                               const uint32_t* __restrict__ gap, const uint32_t* __restrict__ tsum,
+                                               unsigned long long* __restrict__ part_u2,
+                                               double* __restrict__ part_ap) {
   static_assert(AU_WAVES == 4, "red[]");
   __shared__ uint32_t red[AU_WAVES], sc[16];
   __shared__ double sd[AU_THREADS];
   __shared__ unsigned long long su[AU_THREADS];
   if (auc_idle(hdr, max_pos)) return;
   const AucBins bins = auc_bins(hdr, eq, gap);
-  const unsigned long long t0 = (unsigned long long)blockIdx.x * AU_TILE;
+  const unsigned long long t0 = (unsigned long long)bx * AU_TILE;
   if (bins.U > max_pos || t0 >= bins.U) return;  // block-uniform
   const int t = threadIdx.x;
   const unsigned long long P = hdr->pos, N = hdr->neg;
   uint32_t before = 0;  // the negatives of the tiles before this one
-  for (uint32_t i = t; i < blockIdx.x; i += AU_THREADS) before += tsum[i];
+  for (uint32_t i = t; i < (uint32_t)bx; i += AU_THREADS) before += tsum[i];
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
   if ((t & 63) == 0) red[t >> 6] = before;
@@ -607,14 +609,15 @@ __global__ __launch_bounds__(AU_THREADS) void k_auc_terms(const AucHdr* __restri
     if (t < off) sd[t] += sd[t + off], su[t] += su[t + off];
     __syncthreads();
   }
-  if (t == 0) part_ap[blockIdx.x] = sd[0], part_u2[blockIdx.x] = su[0];
+  if (t == 0) part_ap[bx] = sd[0], part_u2[bx] = su[0];
 }
 
-// One block: the tiles' shares folded (thread t: tiles t, t + 1024, .. in order, then a fixed tree), the record
-__global__ __launch_bounds__(AU_ONE_THREADS) void k_auc_finish(const AucHdr* __restrict__ hdr, uint32_t max_pos,
-                                                               const unsigned long long* __restrict__ part_u2,
-                                                               const double* __restrict__ part_ap,
-                                                               di_auc_metrics* __restrict__ out) {
+// One block per complex: the tiles' shares folded (thread t: tiles t, t + 1024, .. in order, then a fixed tree),
+// the record
+__device__ __forceinline__ void auc_finish_body(const AucHdr* __restrict__ hdr, uint32_t max_pos,
+                                                const unsigned long long* __restrict__ part_u2,
+                                                const double* __restrict__ part_ap,
+                                                di_auc_metrics* __restrict__ out) {
   __shared__ double sd[AU_ONE_THREADS];
   __shared__ unsigned long long su[AU_ONE_THREADS];
   const int t = threadIdx.x;
@@ -651,10 +654,205 @@ __global__ __launch_bounds__(AU_ONE_THREADS) void k_auc_finish(const AucHdr* __r
   }
 }
 
+// ---------------------------------------------------------------- entry points: one complex
+__global__ __launch_bounds__(AU_THREADS) void k_auc_collect(const float* __restrict__ probs,
+                                                            const uint8_t* __restrict__ labels, int n, int nv, int per,
+                                                            uint32_t max_pos, AucHdr* __restrict__ hdr,
+                                                            uint32_t* __restrict__ keys) {
+  auc_collect_body(blockIdx.x, probs, labels, n, nv, per, max_pos, hdr, keys);
+}
+__global__ __launch_bounds__(AU_ONE_THREADS) void k_auc_small(AucHdr* __restrict__ hdr, uint32_t max_pos,
+                                                              const uint32_t* __restrict__ keys,
+                                                              uint32_t* __restrict__ uk, uint32_t* __restrict__ upos) {
+  auc_small_body(hdr, max_pos, keys, uk, upos);
+}
+__global__ __launch_bounds__(AU_THREADS) void k_auc_rhist(const AucHdr* __restrict__ hdr, uint32_t max_pos, int nws,
+                                                          int shift, const uint32_t* __restrict__ src,
+                                                          uint32_t* __restrict__ whist) {
+  auc_rhist_body(blockIdx.x, hdr, max_pos, nws, shift, src, whist);
+}
+__global__ __launch_bounds__(AU_THREADS) void k_auc_rscan(const AucHdr* __restrict__ hdr, uint32_t max_pos, int nws,
+                                                          uint32_t* __restrict__ whist, uint32_t* __restrict__ dtot) {
+  auc_rscan_body(blockIdx.x, hdr, max_pos, nws, whist, dtot);
+}
+__global__ __launch_bounds__(AU_THREADS) void k_auc_rscatter(const AucHdr* __restrict__ hdr, uint32_t max_pos, int nws,
+                                                             int shift, const uint32_t* __restrict__ src,
+                                                             const uint32_t* __restrict__ whist,
+                                                             const uint32_t* __restrict__ dtot,
+                                                             uint32_t* __restrict__ dst) {
+  auc_rscatter_body(blockIdx.x, hdr, max_pos, nws, shift, src, whist, dtot, dst);
+}
+__global__ __launch_bounds__(AU_THREADS) void k_auc_heads(const AucHdr* __restrict__ hdr, uint32_t max_pos, int nws,
+                                                          const uint32_t* __restrict__ keys,
+                                                          uint32_t* __restrict__ wheads) {
+  auc_heads_body(blockIdx.x, hdr, max_pos, nws, keys, wheads);
+}
+__global__ __launch_bounds__(AU_THREADS) void k_auc_uniq(AucHdr* __restrict__ hdr, uint32_t max_pos, int nws,
+                                                         const uint32_t* __restrict__ keys,
+                                                         const uint32_t* __restrict__ wheads, uint32_t* __restrict__ uk,
+                                                         uint32_t* __restrict__ upos) {
+  auc_uniq_body(blockIdx.x, hdr, max_pos, nws, keys, wheads, uk, upos);
+}
+__global__ __launch_bounds__(AU_THREADS) void k_auc_bin(const float* __restrict__ probs,
+                                                        const uint8_t* __restrict__ labels, int n, int nv, int per,
+                                                        uint32_t max_pos, AucHdr* __restrict__ hdr,
+                                                        const uint32_t* __restrict__ uk, uint32_t* __restrict__ eq,
+                                                        uint32_t* __restrict__ gap) {
+  auc_bin_body(blockIdx.x, probs, labels, n, nv, per, max_pos, hdr, uk, eq, gap);
+}
+__global__ __launch_bounds__(AU_THREADS) void k_auc_tiles(const AucHdr* __restrict__ hdr, uint32_t max_pos,
+                                                          const uint32_t* __restrict__ eq,
+                                                          const uint32_t* __restrict__ gap,
+                                                          uint32_t* __restrict__ tsum) {
+  auc_tiles_body(blockIdx.x, hdr, max_pos, eq, gap, tsum);
+}
+__global__ __launch_bounds__(AU_THREADS) void k_auc_terms(const AucHdr* __restrict__ hdr, uint32_t max_pos,
+                                                          const uint32_t* __restrict__ upos,
+                                                          const uint32_t* __restrict__ eq,
+                                                          const uint32_t* __restrict__ gap,
+                                                          const uint32_t* __restrict__ tsum,
+                                                          unsigned long long* __restrict__ part_u2,
+                                                          double* __restrict__ part_ap) {
+  auc_terms_body(blockIdx.x, hdr, max_pos, upos, eq, gap, tsum, part_u2, part_ap);
+}
+__global__ __launch_bounds__(AU_ONE_THREADS) void k_auc_finish(const AucHdr* __restrict__ hdr, uint32_t max_pos,
+                                                               const unsigned long long* __restrict__ part_u2,
+                                                               const double* __restrict__ part_ap,
+                                                               di_auc_metrics* __restrict__ out) {
+  auc_finish_body(hdr, max_pos, part_u2, part_ap, out);
+}
+
+// ---------------------------------------------------------------- entry points: the batch
+// Grid (the batch's largest block count of the stage, count): block (x, y) works on complex y, whose
+// descriptor it reads from the device table, and returns at once when x is past that complex's own
+// block count for the stage (the map passes: auc_geo(n).nb; the sort: nws / AU_WAVES; the sums:
+// auc_tile_blocks(max_pos)). Geometry and workspace arrays are auc_geo / auc_work of that complex's n
+// and max_pos, as in the single call, so every output has the single call's bits. Workspace: the
+// cleared part (AucHdr, eq, gap) of every complex first, contiguous: one memset; then each complex's
+// remaining arrays.
+__host__ __device__ static inline int auc_tile_blocks(int64_t max_pos) {
+  return (int)((max_pos + AU_TILE - 1) / AU_TILE);
+}
+struct AucCtx {
+  int n;
+  uint32_t max_pos;
+  AucGeo g;
+  AucWork w;
+};
+__device__ __forceinline__ AucCtx auc_ctx(const di_auc_item& it, char* __restrict__ work) {
+  AucCtx c;
+  c.n = (int)it.n;
+  c.max_pos = (uint32_t)it.max_pos;
+  c.g = auc_geo(it.n);
+  c.w = auc_work(work + it.hdr_off, work + it.work_off, it.max_pos);
+  return c;
+}
+
+__global__ __launch_bounds__(AU_THREADS) void k_auc_collect_b(const di_auc_item* __restrict__ items,
+                                                              char* __restrict__ work) {
+  const di_auc_item& it = items[blockIdx.y];
+  const AucCtx c = auc_ctx(it, work);
+  if ((int)blockIdx.x >= c.g.nb) return;
+  auc_collect_body(blockIdx.x, it.probs, it.labels, c.n, c.g.nv, c.g.per, c.max_pos, c.w.hdr, c.w.keys_a);
+}
+__global__ __launch_bounds__(AU_ONE_THREADS) void k_auc_small_b(const di_auc_item* __restrict__ items,
+                                                                char* __restrict__ work) {
+  const AucCtx c = auc_ctx(items[blockIdx.y], work);
+  auc_small_body(c.w.hdr, c.max_pos, c.w.keys_a, c.w.uk, c.w.upos);
+}
+// flip: the pass reads keys_b and writes keys_a (passes 1 and 3)
+__global__ __launch_bounds__(AU_THREADS) void k_auc_rhist_b(const di_auc_item* __restrict__ items,
+                                                            char* __restrict__ work, int shift, int flip) {
+  const AucCtx c = auc_ctx(items[blockIdx.y], work);
+  if ((int)blockIdx.x >= c.w.nws / AU_WAVES) return;
+  auc_rhist_body(blockIdx.x, c.w.hdr, c.max_pos, c.w.nws, shift, flip ? c.w.keys_b : c.w.keys_a, c.w.whist);
+}
+__global__ __launch_bounds__(AU_THREADS) void k_auc_rscan_b(const di_auc_item* __restrict__ items,
+                                                            char* __restrict__ work) {
+  const AucCtx c = auc_ctx(items[blockIdx.y], work);
+  auc_rscan_body(blockIdx.x, c.w.hdr, c.max_pos, c.w.nws, c.w.whist, c.w.dtot);
+}
+__global__ __launch_bounds__(AU_THREADS) void k_auc_rscatter_b(const di_auc_item* __restrict__ items,
+                                                               char* __restrict__ work, int shift, int flip) {
+  const AucCtx c = auc_ctx(items[blockIdx.y], work);
+  if ((int)blockIdx.x >= c.w.nws / AU_WAVES) return;
+  auc_rscatter_body(blockIdx.x, c.w.hdr, c.max_pos, c.w.nws, shift, flip ? c.w.keys_b : c.w.keys_a, c.w.whist,
+                    c.w.dtot, flip ? c.w.keys_a : c.w.keys_b);
+}
+__global__ __launch_bounds__(AU_THREADS) void k_auc_heads_b(const di_auc_item* __restrict__ items,
+                                                            char* __restrict__ work) {
+  const AucCtx c = auc_ctx(items[blockIdx.y], work);
+  if ((int)blockIdx.x >= c.w.nws / AU_WAVES) return;
+  auc_heads_body(blockIdx.x, c.w.hdr, c.max_pos, c.w.nws, c.w.keys_a, c.w.wheads);
+}
+__global__ __launch_bounds__(AU_THREADS) void k_auc_uniq_b(const di_auc_item* __restrict__ items,
+                                                           char* __restrict__ work) {
+  const AucCtx c = auc_ctx(items[blockIdx.y], work);
+  if ((int)blockIdx.x >= c.w.nws / AU_WAVES) return;
+  auc_uniq_body(blockIdx.x, c.w.hdr, c.max_pos, c.w.nws, c.w.keys_a, c.w.wheads, c.w.uk, c.w.upos);
+}
+__global__ __launch_bounds__(AU_THREADS) void k_auc_bin_b(const di_auc_item* __restrict__ items,
+                                                          char* __restrict__ work) {
+  const di_auc_item& it = items[blockIdx.y];
+  const AucCtx c = auc_ctx(it, work);
+  if ((int)blockIdx.x >= c.g.nb) return;
+  auc_bin_body(blockIdx.x, it.probs, it.labels, c.n, c.g.nv, c.g.per, c.max_pos, c.w.hdr, c.w.uk, c.w.eq, c.w.gap);
+}
+__global__ __launch_bounds__(AU_THREADS) void k_auc_tiles_b(const di_auc_item* __restrict__ items,
+                                                            char* __restrict__ work) {
+  const di_auc_item& it = items[blockIdx.y];
+  const AucCtx c = auc_ctx(it, work);
+  if ((int)blockIdx.x >= auc_tile_blocks(it.max_pos)) return;
+  auc_tiles_body(blockIdx.x, c.w.hdr, c.max_pos, c.w.eq, c.w.gap, c.w.tsum);
+}
+__global__ __launch_bounds__(AU_THREADS) void k_auc_terms_b(const di_auc_item* __restrict__ items,
+                                                            char* __restrict__ work) {
+  const di_auc_item& it = items[blockIdx.y];
+  const AucCtx c = auc_ctx(it, work);
+  if ((int)blockIdx.x >= auc_tile_blocks(it.max_pos)) return;
+  auc_terms_body(blockIdx.x, c.w.hdr, c.max_pos, c.w.upos, c.w.eq, c.w.gap, c.w.tsum, c.w.part_u2, c.w.part_ap);
+}
+__global__ __launch_bounds__(AU_ONE_THREADS) void k_auc_finish_b(const di_auc_item* __restrict__ items,
+                                                                 char* __restrict__ work) {
+  const di_auc_item& it = items[blockIdx.y];
+  const AucCtx c = auc_ctx(it, work);
+  auc_finish_body(c.w.hdr, c.max_pos, c.w.part_u2, c.w.part_ap, it.out);
+}
+
 static int auc_check_sizes(int64_t n, int64_t max_pos) {
   if (n < 1 || max_pos < 1 || max_pos > n) return DI_EINVAL;
   if (n >= AU_MAX_N) return DI_ERANGE;
   return DI_OK;
+}
+
+// every refusal of di_contact_auc, for one complex
+static int auc_check_call(const float* probs, const uint8_t* labels, int64_t n, int64_t max_pos,
+                          const di_auc_metrics* out, const void* work) {
+  const int rc = auc_check_sizes(n, max_pos);
+  if (rc != DI_OK) return rc;
+  if (!probs || !labels || !out || !work) return DI_EINVAL;
+  if (((uintptr_t)probs & 15) || ((uintptr_t)work & 15)) return DI_EINVAL;
+  return DI_OK;
+}
+
+// The batch workspace's layout from the items' sizes: off[i] = {hdr_off, work_off} of item i where off
+// is given; *clear = the bytes at the front that the call clears; the total, or the code of the first
+// item whose sizes the single call would refuse. Every part is a multiple of 16 B.
+static int64_t auc_batch_layout(const di_auc_item* items, int32_t count, int64_t (*off)[2], int64_t* clear) {
+  int64_t at = 0;
+  for (int32_t i = 0; i < count; ++i) {
+    const int rc = auc_check_sizes(items[i].n, items[i].max_pos);
+    if (rc != DI_OK) return rc;
+    if (off) off[i][0] = at;
+    at += auc_work(nullptr, nullptr, items[i].max_pos).clear_bytes;
+  }
+  if (clear) *clear = at;
+  for (int32_t i = 0; i < count; ++i) {
+    const AucWork w = auc_work(nullptr, nullptr, items[i].max_pos);
+    if (off) off[i][1] = at;
+    at += w.bytes - w.clear_bytes;
+  }
+  return at;
 }
 
 }  // namespace di
@@ -664,25 +862,24 @@ using namespace di;
 extern "C" int64_t di_contact_auc_work_bytes(int64_t n, int64_t max_pos) {
   const int rc = auc_check_sizes(n, max_pos);
   if (rc != DI_OK) return rc;
-  return auc_work(nullptr, max_pos).bytes;
+  return auc_work(nullptr, nullptr, max_pos).bytes;
 }
 
 extern "C" int di_contact_auc(const float* probs, const uint8_t* labels, int64_t n64, int64_t max_pos64,
                               di_auc_metrics* out, void* work, void* stream) {
-  const int rc = auc_check_sizes(n64, max_pos64);
+  const int rc = auc_check_call(probs, labels, n64, max_pos64, out, work);
   if (rc != DI_OK) return rc;
-  if (!probs || !labels || !out || !work) return DI_EINVAL;
-  if (((uintptr_t)probs & 15) || ((uintptr_t)work & 15)) return DI_EINVAL;
 
   const int n = (int)n64;
   const uint32_t max_pos = (uint32_t)max_pos64;
   const AucGeo g = auc_geo(n);
-  const AucWork w = auc_work(work, max_pos64);
+  const int64_t clear_bytes = auc_work(nullptr, nullptr, max_pos64).clear_bytes;
+  const AucWork w = auc_work(work, reinterpret_cast<char*>(work) + clear_bytes, max_pos64);
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(w.hdr, 0, (size_t)w.clear_bytes, s);
   if (e != hipSuccess) return (int)e;
   const dim3 grid(g.nb), block(AU_THREADS), one(1), wide(AU_ONE_THREADS), sgrid(w.nws / AU_WAVES);
-  const dim3 tgrid((unsigned)((max_pos64 + AU_TILE - 1) / AU_TILE));
+  const dim3 tgrid((unsigned)auc_tile_blocks(max_pos64));
   hipLaunchKernelGGL(k_auc_collect, grid, block, 0, s, probs, labels, n, g.nv, g.per, max_pos, w.hdr, w.keys_a);
   hipLaunchKernelGGL(k_auc_small, one, wide, 0, s, w.hdr, max_pos, w.keys_a, w.uk, w.upos);
   uint32_t *src = w.keys_a, *dst = w.keys_b;
@@ -705,3 +902,59 @@ extern "C" int di_contact_auc(const float* probs, const uint8_t* labels, int64_t
   e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
 }
+
+extern "C" int64_t di_contact_auc_batch_work_bytes(di_auc_item* items, int32_t count) {
+  if (!items || count < 1) return DI_EINVAL;
+  if (count > DI_BATCH_MAX) return DI_ERANGE;
+  int64_t off[DI_BATCH_MAX][2];
+  const int64_t total = auc_batch_layout(items, count, off, nullptr);
+  if (total < 0) return total;
+  for (int32_t i = 0; i < count; ++i) items[i].hdr_off = off[i][0], items[i].work_off = off[i][1];
+  return total;
+}
+
+extern "C" int di_contact_auc_batch(const di_auc_item* items, const di_auc_item* items_dev, int32_t count,
+                                    void* work, void* stream) {
+  if (count < 1 || !items || !items_dev) return DI_EINVAL;
+  if (count > DI_BATCH_MAX) return DI_ERANGE;
+  int max_nb = 1, max_sort = 1, max_tiles = 1;
+  for (int32_t i = 0; i < count; ++i) {
+    const di_auc_item& it = items[i];
+    const int rc = auc_check_call(it.probs, it.labels, it.n, it.max_pos, it.out, work);
+    if (rc != DI_OK) return rc;
+    const int nb = auc_geo(it.n).nb, sort = auc_work(nullptr, nullptr, it.max_pos).nws / AU_WAVES;
+    const int tiles = auc_tile_blocks(it.max_pos);
+    max_nb = nb > max_nb ? nb : max_nb;
+    max_sort = sort > max_sort ? sort : max_sort;
+    max_tiles = tiles > max_tiles ? tiles : max_tiles;
+  }
+  // the offsets are those di_contact_auc_batch_work_bytes fills (every item's sizes passed above)
+  int64_t off[DI_BATCH_MAX][2], clear_bytes = 0;
+  if (auc_batch_layout(items, count, off, &clear_bytes) < 0) return DI_EINVAL;
+  for (int32_t i = 0; i < count; ++i)
+    if (items[i].hdr_off != off[i][0] || items[i].work_off != off[i][1]) return DI_EINVAL;
+
+  hipStream_t s = (hipStream_t)stream;
+  char* w = reinterpret_cast<char*>(work);
+  hipError_t e = hipMemsetAsync(w, 0, (size_t)clear_bytes, s);
+  if (e != hipSuccess) return (int)e;
+  const dim3 block(AU_THREADS), wide(AU_ONE_THREADS), one(1, count);
+  const dim3 grid(max_nb, count), sgrid(max_sort, count), dgrid(256, count), tgrid(max_tiles, count);
+  hipLaunchKernelGGL(k_auc_collect_b, grid, block, 0, s, items_dev, w);
+  hipLaunchKernelGGL(k_auc_small_b, one, wide, 0, s, items_dev, w);
+  for (int pass = 0; pass < 4; ++pass) {
+    hipLaunchKernelGGL(k_auc_rhist_b, sgrid, block, 0, s, items_dev, w, 8 * pass, pass & 1);
+    hipLaunchKernelGGL(k_auc_rscan_b, dgrid, block, 0, s, items_dev, w);
+    hipLaunchKernelGGL(k_auc_rscatter_b, sgrid, block, 0, s, items_dev, w, 8 * pass, pass & 1);
+  }
+  // four passes: the sorted keys are back in keys_a
+  hipLaunchKernelGGL(k_auc_heads_b, sgrid, block, 0, s, items_dev, w);
+  hipLaunchKernelGGL(k_auc_uniq_b, sgrid, block, 0, s, items_dev, w);
+  hipLaunchKernelGGL(k_auc_bin_b, grid, block, 0, s, items_dev, w);
+  hipLaunchKernelGGL(k_auc_tiles_b, tgrid, block, 0, s, items_dev, w);
+  hipLaunchKernelGGL(k_auc_terms_b, tgrid, block, 0, s, items_dev, w);
+  hipLaunchKernelGGL(k_auc_finish_b, one, wide, 0, s, items_dev, w);
+  e = hipGetLastError();
+  return e == hipSuccess ? DI_OK : (int)e;
+}
+

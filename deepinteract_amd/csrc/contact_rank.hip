@@ -30,6 +30,8 @@
 // Algorithmic bytes per element (fp32 / bf16 logits): 8 / 4 read + 4 written by k_rank_probs (+ 1
 // with labels), then 3 x 4 read of the map (two histograms, the count): 24 / 20 B; the compaction
 // re-reads only slices that hold a candidate.
+// di_contact_rank_batch runs the same sequence once for many complexes (grid y = complex; "the batch"
+// below): the same kernel bodies on the same per-complex geometry, so the same bits per complex.
 // Elements are handled as 4-element vectors of the (16-B aligned) map; the class planes of the
 // logits start at any element alignment (n odd), so they are read with unaligned 16-B / 8-B loads.
 #include <float.h>
@@ -67,11 +69,12 @@ struct RankWork {
 constexpr int64_t RK_FIXED_BYTES =
     (int64_t)sizeof(RankHdr) + 2 * RK_MAX_WAVES * (int64_t)sizeof(uint32_t) + RK_MAX_BLOCKS * (int64_t)sizeof(double);
 
-static RankWork rank_work(void* work) {
+// hdr: the cleared header; rest: everything else (directly behind the header in a single call's
+// workspace; in a batch the headers of all complexes are contiguous, so that one memset clears them)
+__host__ __device__ static inline RankWork rank_work(void* hdr, void* rest) {
   RankWork w;
-  char* p = reinterpret_cast<char*>(work);
-  w.hdr = reinterpret_cast<RankHdr*>(p);
-  w.wave_eq = reinterpret_cast<uint32_t*>(p + sizeof(RankHdr));
+  w.hdr = reinterpret_cast<RankHdr*>(hdr);
+  w.wave_eq = reinterpret_cast<uint32_t*>(rest);
   w.wave_gt = w.wave_eq + RK_MAX_WAVES;
   w.ce_part = reinterpret_cast<double*>(w.wave_gt + RK_MAX_WAVES);
   w.cand = reinterpret_cast<unsigned long long*>(w.ce_part + RK_MAX_BLOCKS);
@@ -83,7 +86,7 @@ static RankWork rank_work(void* work) {
 struct RankGeo {
   int nv, nb, nw, per;
 };
-static RankGeo rank_geo(int64_t n) {
+__host__ __device__ static inline RankGeo rank_geo(int64_t n) {
   RankGeo g;
   g.nv = (int)((n + 3) / 4);
   const int64_t want = (g.nv + RK_THREADS * 4 - 1) / (RK_THREADS * 4);  // >= 4 vectors per lane
@@ -160,15 +163,18 @@ __device__ __forceinline__ void lds_hist_flush(const uint32_t* h, int bins, uint
 }
 
 // ---------------------------------------------------------------- pass 1
+// Every stage is a __device__ body behind two thin entry points: k_x for one complex and k_x_b for a
+// batch, where the grid's y index names the complex (see "the batch" below). bx is the block's index
+// inside its complex.
 template <typename T, bool LAB>
-__global__ __launch_bounds__(RK_THREADS) void k_rank_probs(const T* __restrict__ logits, int n, int nv, int per,
-                                                           const uint8_t* __restrict__ labels, float threshold,
-                                                           float* __restrict__ probs, RankHdr* __restrict__ hdr,
-                                                           double* __restrict__ ce_part) {
+__device__ __forceinline__ void rank_probs_body(const int bx, const T* __restrict__ logits, int n, int nv, int per,
+                                                const uint8_t* __restrict__ labels, float threshold,
+                                                float* __restrict__ probs, RankHdr* __restrict__ hdr,
+                                                double* __restrict__ ce_part) {
   __shared__ uint32_t h[2048];
   lds_hist_clear(h, 2048);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lo = (blockIdx.x * RK_WAVES + wave) * per;
+  const int lo = (bx * RK_WAVES + wave) * per;
   const int hi = lo + per < nv ? lo + per : nv;
   const T* __restrict__ l0 = logits;
   const T* __restrict__ l1 = logits + n;
@@ -239,7 +245,7 @@ __global__ __launch_bounds__(RK_THREADS) void k_rank_probs(const T* __restrict__
         s += red_ce[w];
         for (int j = 0; j < 4; ++j) c[j] += red_c[j][w];
       }
-      ce_part[blockIdx.x] = s;  // folded in block order by k_rank_finish
+      ce_part[bx] = s;  // folded in block order by k_rank_finish
       if (c[0] + c[2]) atomicAdd(&hdr->cnt[0], c[0] + c[2]);
       for (int j = 0; j < 4; ++j)
         if (c[j]) atomicAdd(&hdr->cnt[1 + j], c[j]);
@@ -274,7 +280,7 @@ struct RankSel {
   uint32_t prefix, krem;
 };
 template <int STEP>
-__device__ __forceinline__ RankSel rank_select(RankHdr* __restrict__ hdr, uint32_t k) {
+__device__ __forceinline__ RankSel rank_select(const int bx, RankHdr* __restrict__ hdr, uint32_t k) {
   constexpr int BINS = STEP == 2 ? 1024 : 2048;
   constexpr int BITS = STEP == 2 ? 10 : 11;
   constexpr int PER = BINS / RK_THREADS;
@@ -302,22 +308,22 @@ __device__ __forceinline__ RankSel rank_select(RankHdr* __restrict__ hdr, uint32
   }
   __syncthreads();
   const RankSel r = {res[0], res[1]};
-  if (blockIdx.x == 0 && t == 0) hdr->sel[STEP][0] = r.prefix, hdr->sel[STEP][1] = r.krem;
+  if (bx == 0 && t == 0) hdr->sel[STEP][0] = r.prefix, hdr->sel[STEP][1] = r.krem;
   return r;
 }
 
 // PASS 1: bits 20..10 of the keys whose bits 31..21 equal the prefix; PASS 2: bits 9..0 of those whose
 // bits 31..10 do
 template <int PASS>
-__global__ __launch_bounds__(RK_THREADS) void k_rank_hist(const float* __restrict__ probs, int n, int nv, int per,
-                                                          uint32_t k, RankHdr* __restrict__ hdr) {
+__device__ __forceinline__ void rank_hist_body(const int bx, const float* __restrict__ probs, int n, int nv, int per,
+                                               uint32_t k, RankHdr* __restrict__ hdr) {
   constexpr int BINS = PASS == 1 ? 2048 : 1024;
   constexpr int SHIFT = PASS == 1 ? 21 : 10;
   __shared__ uint32_t h[BINS];
   lds_hist_clear(h, BINS);
-  const uint32_t prefix = rank_select<PASS - 1>(hdr, k).prefix;
+  const uint32_t prefix = rank_select<PASS - 1>(bx, hdr, k).prefix;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lo = (blockIdx.x * RK_WAVES + wave) * per;
+  const int lo = (bx * RK_WAVES + wave) * per;
   const int hi = lo + per < nv ? lo + per : nv;
 #pragma unroll 2
   for (int v = lo + lane; v < hi; v += 64) {
@@ -334,12 +340,11 @@ __global__ __launch_bounds__(RK_THREADS) void k_rank_hist(const float* __restric
 
 // ---------------------------------------------------------------- ordered compaction
 // the last select fixes the threshold key T (hdr->sel[2]: T, and how many elements equal to T to take)
-__global__ __launch_bounds__(RK_THREADS) void k_rank_count(const float* __restrict__ probs, int n, int nv, int per,
-                                                           uint32_t k, RankHdr* __restrict__ hdr,
-                                                           uint32_t* __restrict__ wave_eq,
-                                                           uint32_t* __restrict__ wave_gt) {
-  const uint32_t T = rank_select<2>(hdr, k).prefix;
-  const int lane = threadIdx.x & 63, w = blockIdx.x * RK_WAVES + (threadIdx.x >> 6);
+__device__ __forceinline__ void rank_count_body(const int bx, const float* __restrict__ probs, int n, int nv, int per,
+                                                uint32_t k, RankHdr* __restrict__ hdr,
+                                                uint32_t* __restrict__ wave_eq, uint32_t* __restrict__ wave_gt) {
+  const uint32_t T = rank_select<2>(bx, hdr, k).prefix;
+  const int lane = threadIdx.x & 63, w = bx * RK_WAVES + (threadIdx.x >> 6);
   const int lo = w * per;
   const int hi = lo + per < nv ? lo + per : nv;
   uint32_t eq = 0, gt = 0;
@@ -369,16 +374,16 @@ __global__ __launch_bounds__(RK_THREADS) void k_rank_count(const float* __restri
 // equal to T behind them. A block without a candidate returns at once; the others sum the counts of
 // the waves before them (the scan across blocks, without a launch of its own). A wave's rank inside
 // its 64-vector tile comes from ballots: lanes below it, then its own earlier elements.
-__global__ __launch_bounds__(RK_THREADS) void k_rank_compact(const float* __restrict__ probs, int n, int nv, int per,
-                                                             int k, const RankHdr* __restrict__ hdr,
-                                                             const uint32_t* __restrict__ wave_eq,
-                                                             const uint32_t* __restrict__ wave_gt,
-                                                             unsigned long long* __restrict__ cand) {
+__device__ __forceinline__ void rank_compact_body(const int bx, const float* __restrict__ probs, int n, int nv,
+                                                  int per, int k, const RankHdr* __restrict__ hdr,
+                                                  const uint32_t* __restrict__ wave_eq,
+                                                  const uint32_t* __restrict__ wave_gt,
+                                                  unsigned long long* __restrict__ cand) {
   const uint32_t T = hdr->sel[2][0];
   const uint32_t need = hdr->sel[2][1] < (uint32_t)k ? hdr->sel[2][1] : (uint32_t)k;  // 1 .. k: slots stay below k
   const uint32_t ngt = (uint32_t)k - need;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int w0 = blockIdx.x * RK_WAVES, w = w0 + wave;
+  const int w0 = bx * RK_WAVES, w = w0 + wave;
   uint32_t ceq[RK_WAVES], cgt[RK_WAVES], any = 0;
 #pragma unroll
   for (int i = 0; i < RK_WAVES; ++i) any |= (ceq[i] = wave_eq[w0 + i]) | (cgt[i] = wave_gt[w0 + i]);
@@ -437,8 +442,8 @@ __global__ __launch_bounds__(RK_THREADS) void k_rank_compact(const float* __rest
 }
 
 // ---------------------------------------------------------------- sort and outputs
-// One block. kp: k rounded up to a power of two (<= DI_RANK_MAX_K).
-__global__ __launch_bounds__(RK_ONE_THREADS) void k_rank_finish(
+// One block per complex. kp: k rounded up to a power of two (<= DI_RANK_MAX_K).
+__device__ __forceinline__ void rank_finish_body(
     const float* __restrict__ probs, const uint8_t* __restrict__ labels, int n, int k, int kp,
     const unsigned long long* __restrict__ cand, const RankHdr* __restrict__ hdr, const double* __restrict__ ce_part,
     int nb, int32_t* __restrict__ top_ids, float* __restrict__ top_scores, int32_t* __restrict__ top_hits,
@@ -501,10 +506,120 @@ __global__ __launch_bounds__(RK_ONE_THREADS) void k_rank_finish(
   }
 }
 
+// ---------------------------------------------------------------- entry points: one complex
+template <typename T, bool LAB>
+__global__ __launch_bounds__(RK_THREADS) void k_rank_probs(const T* __restrict__ logits, int n, int nv, int per,
+                                                           const uint8_t* __restrict__ labels, float threshold,
+                                                           float* __restrict__ probs, RankHdr* __restrict__ hdr,
+                                                           double* __restrict__ ce_part) {
+  rank_probs_body<T, LAB>(blockIdx.x, logits, n, nv, per, labels, threshold, probs, hdr, ce_part);
+}
+template <int PASS>
+__global__ __launch_bounds__(RK_THREADS) void k_rank_hist(const float* __restrict__ probs, int n, int nv, int per,
+                                                          uint32_t k, RankHdr* __restrict__ hdr) {
+  rank_hist_body<PASS>(blockIdx.x, probs, n, nv, per, k, hdr);
+}
+__global__ __launch_bounds__(RK_THREADS) void k_rank_count(const float* __restrict__ probs, int n, int nv, int per,
+                                                           uint32_t k, RankHdr* __restrict__ hdr,
+                                                           uint32_t* __restrict__ wave_eq,
+                                                           uint32_t* __restrict__ wave_gt) {
+  rank_count_body(blockIdx.x, probs, n, nv, per, k, hdr, wave_eq, wave_gt);
+}
+__global__ __launch_bounds__(RK_THREADS) void k_rank_compact(const float* __restrict__ probs, int n, int nv, int per,
+                                                             int k, const RankHdr* __restrict__ hdr,
+                                                             const uint32_t* __restrict__ wave_eq,
+                                                             const uint32_t* __restrict__ wave_gt,
+                                                             unsigned long long* __restrict__ cand) {
+  rank_compact_body(blockIdx.x, probs, n, nv, per, k, hdr, wave_eq, wave_gt, cand);
+}
+__global__ __launch_bounds__(RK_ONE_THREADS) void k_rank_finish(
+    const float* __restrict__ probs, const uint8_t* __restrict__ labels, int n, int k, int kp,
+    const unsigned long long* __restrict__ cand, const RankHdr* __restrict__ hdr, const double* __restrict__ ce_part,
+    int nb, int32_t* __restrict__ top_ids, float* __restrict__ top_scores, int32_t* __restrict__ top_hits,
+    di_rank_metrics* __restrict__ metrics) {
+  rank_finish_body(probs, labels, n, k, kp, cand, hdr, ce_part, nb, top_ids, top_scores, top_hits, metrics);
+}
+
+// ---------------------------------------------------------------- entry points: the batch
+// Grid (the batch's largest block count, count): block (x, y) works on complex y, whose descriptor it
+// reads from the device table, and returns at once when x is past that complex's own block count. The
+// geometry is rank_geo of that complex's n, as in the single call, so every output has the single
+// call's bits. Workspace: the RankHdr of every complex first, contiguous (item i's at
+// i * sizeof(RankHdr): one memset), then each complex's wave counts, loss partials and candidates.
+struct RankCtx {
+  int n;
+  RankGeo g;
+  RankWork w;
+};
+__device__ __forceinline__ RankCtx rank_ctx(const di_rank_item& it, char* __restrict__ work) {
+  RankCtx c;
+  c.n = it.l1 * it.l2;
+  c.g = rank_geo(c.n);
+  c.w = rank_work(work + it.hdr_off, work + it.work_off);
+  return c;
+}
+
+template <typename T, bool LAB>
+__global__ __launch_bounds__(RK_THREADS) void k_rank_probs_b(const di_rank_item* __restrict__ items,
+                                                             char* __restrict__ work, float threshold) {
+  const di_rank_item& it = items[blockIdx.y];
+  const RankCtx c = rank_ctx(it, work);
+  if ((int)blockIdx.x >= c.g.nb) return;
+  rank_probs_body<T, LAB>(blockIdx.x, (const T*)it.logits, c.n, c.g.nv, c.g.per, it.labels, threshold, it.probs,
+                          c.w.hdr, c.w.ce_part);
+}
+template <int PASS>
+__global__ __launch_bounds__(RK_THREADS) void k_rank_hist_b(const di_rank_item* __restrict__ items,
+                                                            char* __restrict__ work) {
+  const di_rank_item& it = items[blockIdx.y];
+  const RankCtx c = rank_ctx(it, work);
+  if ((int)blockIdx.x >= c.g.nb) return;
+  rank_hist_body<PASS>(blockIdx.x, it.probs, c.n, c.g.nv, c.g.per, (uint32_t)it.k, c.w.hdr);
+}
+__global__ __launch_bounds__(RK_THREADS) void k_rank_count_b(const di_rank_item* __restrict__ items,
+                                                             char* __restrict__ work) {
+  const di_rank_item& it = items[blockIdx.y];
+  const RankCtx c = rank_ctx(it, work);
+  if ((int)blockIdx.x >= c.g.nb) return;
+  rank_count_body(blockIdx.x, it.probs, c.n, c.g.nv, c.g.per, (uint32_t)it.k, c.w.hdr, c.w.wave_eq, c.w.wave_gt);
+}
+__global__ __launch_bounds__(RK_THREADS) void k_rank_compact_b(const di_rank_item* __restrict__ items,
+                                                               char* __restrict__ work) {
+  const di_rank_item& it = items[blockIdx.y];
+  const RankCtx c = rank_ctx(it, work);
+  if ((int)blockIdx.x >= c.g.nb) return;
+  rank_compact_body(blockIdx.x, it.probs, c.n, c.g.nv, c.g.per, it.k, c.w.hdr, c.w.wave_eq, c.w.wave_gt, c.w.cand);
+}
+__global__ __launch_bounds__(RK_ONE_THREADS) void k_rank_finish_b(const di_rank_item* __restrict__ items,
+                                                                  char* __restrict__ work) {
+  const di_rank_item& it = items[blockIdx.y];
+  const RankCtx c = rank_ctx(it, work);
+  int kp = 1;
+  while (kp < it.k) kp <<= 1;
+  rank_finish_body(it.probs, it.labels, c.n, it.k, kp, c.w.cand, c.w.hdr, c.w.ce_part, c.g.nb, it.top_ids,
+                   it.top_scores, it.top_hits, it.metrics);
+}
+
 static int rank_check_sizes(int64_t n, int64_t k) {
   if (n < 1 || k < 1 || k > n) return DI_EINVAL;
   if (k > DI_RANK_MAX_K || n >= RK_MAX_N) return DI_ERANGE;
   return DI_OK;
+}
+
+// every refusal of di_contact_rank, for one complex
+static int rank_check_call(int32_t dtype, const void* logits, int32_t l1, int32_t l2, int32_t k, const uint8_t* labels,
+                           float threshold, const float* probs, const int32_t* top_ids, const float* top_scores,
+                           const int32_t* top_hits, const di_rank_metrics* metrics, const void* work) {
+  if (l1 < 1 || l2 < 1) return DI_EINVAL;
+  const int64_t n64 = (int64_t)l1 * (int64_t)l2;  // < 2^62
+  if (k < 1 || k > n64) return DI_EINVAL;
+  if (dtype != DI_F32 && dtype != DI_BF16) return DI_EINVAL;
+  if (!logits || !probs || !top_ids || !top_scores || !work) return DI_EINVAL;
+  const int with = (labels != nullptr) + (top_hits != nullptr) + (metrics != nullptr);
+  if (with != 0 && with != 3) return DI_EINVAL;
+  if (threshold != threshold) return DI_EINVAL;
+  if (((uintptr_t)probs & 15) || ((uintptr_t)work & 15)) return DI_EINVAL;
+  return rank_check_sizes(n64, k);
 }
 
 template <typename T>
@@ -516,6 +631,35 @@ static void launch_probs(const RankGeo& g, const void* logits, int n, const uint
   else
     hipLaunchKernelGGL((k_rank_probs<T, false>), dim3(g.nb), dim3(RK_THREADS), 0, s, (const T*)logits, n, g.nv,
                        g.per, labels, threshold, probs, w.hdr, w.ce_part);
+}
+
+template <typename T>
+static void launch_probs_b(dim3 grid, bool lab, const di_rank_item* items_dev, char* work, float threshold,
+                           hipStream_t s) {
+  if (lab)
+    hipLaunchKernelGGL((k_rank_probs_b<T, true>), grid, dim3(RK_THREADS), 0, s, items_dev, work, threshold);
+  else
+    hipLaunchKernelGGL((k_rank_probs_b<T, false>), grid, dim3(RK_THREADS), 0, s, items_dev, work, threshold);
+}
+
+// what lies behind the headers for one complex, a multiple of 16 B
+static int64_t rank_rest_bytes(int64_t k) {
+  const int64_t b = RK_FIXED_BYTES - (int64_t)sizeof(RankHdr) + k * (int64_t)sizeof(unsigned long long);
+  return (b + 15) / 16 * 16;
+}
+
+// The batch workspace's layout from the items' sizes: off[i] = {hdr_off, work_off} of item i where off
+// is given; the total, or the code of the first item whose sizes the single call would refuse.
+static int64_t rank_batch_layout(const di_rank_item* items, int32_t count, int64_t (*off)[2]) {
+  int64_t at = (int64_t)count * (int64_t)sizeof(RankHdr);
+  for (int32_t i = 0; i < count; ++i) {
+    if (items[i].l1 < 1 || items[i].l2 < 1) return DI_EINVAL;
+    const int rc = rank_check_sizes((int64_t)items[i].l1 * (int64_t)items[i].l2, items[i].k);
+    if (rc != DI_OK) return rc;
+    if (off) off[i][0] = (int64_t)i * (int64_t)sizeof(RankHdr), off[i][1] = at;
+    at += rank_rest_bytes(items[i].k);
+  }
+  return at;
 }
 
 }  // namespace di
@@ -532,21 +676,13 @@ extern "C" int di_contact_rank(int32_t dtype, const void* logits, int32_t l1, in
                                const uint8_t* labels, float threshold, float* probs, int32_t* top_ids,
                                float* top_scores, int32_t* top_hits, di_rank_metrics* metrics, void* work,
                                void* stream) {
-  if (l1 < 1 || l2 < 1) return DI_EINVAL;
-  const int64_t n64 = (int64_t)l1 * (int64_t)l2;  // < 2^62
-  if (k < 1 || k > n64) return DI_EINVAL;
-  if (dtype != DI_F32 && dtype != DI_BF16) return DI_EINVAL;
-  if (!logits || !probs || !top_ids || !top_scores || !work) return DI_EINVAL;
-  const int with = (labels != nullptr) + (top_hits != nullptr) + (metrics != nullptr);
-  if (with != 0 && with != 3) return DI_EINVAL;
-  if (threshold != threshold) return DI_EINVAL;
-  if (((uintptr_t)probs & 15) || ((uintptr_t)work & 15)) return DI_EINVAL;
-  const int rc = rank_check_sizes(n64, k);
+  const int rc = rank_check_call(dtype, logits, l1, l2, k, labels, threshold, probs, top_ids, top_scores, top_hits,
+                                 metrics, work);
   if (rc != DI_OK) return rc;
 
-  const int n = (int)n64;
+  const int n = l1 * l2;
   const RankGeo g = rank_geo(n);
-  const RankWork w = rank_work(work);
+  const RankWork w = rank_work(work, reinterpret_cast<char*>(work) + sizeof(RankHdr));
   int kp = 1;
   while (kp < k) kp <<= 1;
   hipStream_t s = (hipStream_t)stream;
@@ -568,3 +704,53 @@ extern "C" int di_contact_rank(int32_t dtype, const void* logits, int32_t l1, in
   e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
 }
+
+extern "C" int64_t di_contact_rank_batch_work_bytes(di_rank_item* items, int32_t count) {
+  if (!items || count < 1) return DI_EINVAL;
+  if (count > DI_BATCH_MAX) return DI_ERANGE;
+  int64_t off[DI_BATCH_MAX][2];
+  const int64_t total = rank_batch_layout(items, count, off);
+  if (total < 0) return total;
+  for (int32_t i = 0; i < count; ++i) items[i].hdr_off = off[i][0], items[i].work_off = off[i][1];
+  return total;
+}
+
+extern "C" int di_contact_rank_batch(int32_t dtype, const di_rank_item* items, const di_rank_item* items_dev,
+                                     int32_t count, float threshold, void* work, void* stream) {
+  if (count < 1 || !items || !items_dev) return DI_EINVAL;
+  if (count > DI_BATCH_MAX) return DI_ERANGE;
+  int max_nb = 1;
+  for (int32_t i = 0; i < count; ++i) {
+    const di_rank_item& it = items[i];
+    const int rc = rank_check_call(dtype, it.logits, it.l1, it.l2, it.k, it.labels, threshold, it.probs, it.top_ids,
+                                   it.top_scores, it.top_hits, it.metrics, work);
+    if (rc != DI_OK) return rc;
+    // one kernel variant serves the batch: labels for every complex or for none
+    if ((it.labels != nullptr) != (items[0].labels != nullptr)) return DI_EINVAL;
+    const int nb = rank_geo((int64_t)it.l1 * it.l2).nb;
+    max_nb = nb > max_nb ? nb : max_nb;
+  }
+  // the offsets are those di_contact_rank_batch_work_bytes fills (every item's sizes passed above)
+  int64_t off[DI_BATCH_MAX][2];
+  if (rank_batch_layout(items, count, off) < 0) return DI_EINVAL;
+  for (int32_t i = 0; i < count; ++i)
+    if (items[i].hdr_off != off[i][0] || items[i].work_off != off[i][1]) return DI_EINVAL;
+
+  hipStream_t s = (hipStream_t)stream;
+  char* w = reinterpret_cast<char*>(work);
+  hipError_t e = hipMemsetAsync(w, 0, (size_t)count * sizeof(RankHdr), s);
+  if (e != hipSuccess) return (int)e;
+  const dim3 grid(max_nb, count), block(RK_THREADS);
+  if (dtype == DI_BF16)
+    launch_probs_b<u16>(grid, items[0].labels != nullptr, items_dev, w, threshold, s);
+  else
+    launch_probs_b<float>(grid, items[0].labels != nullptr, items_dev, w, threshold, s);
+  hipLaunchKernelGGL(k_rank_hist_b<1>, grid, block, 0, s, items_dev, w);
+  hipLaunchKernelGGL(k_rank_hist_b<2>, grid, block, 0, s, items_dev, w);
+  hipLaunchKernelGGL(k_rank_count_b, grid, block, 0, s, items_dev, w);
+  hipLaunchKernelGGL(k_rank_compact_b, grid, block, 0, s, items_dev, w);
+  hipLaunchKernelGGL(k_rank_finish_b, dim3(1, count), dim3(RK_ONE_THREADS), 0, s, items_dev, w);
+  e = hipGetLastError();
+  return e == hipSuccess ? DI_OK : (int)e;
+}
+

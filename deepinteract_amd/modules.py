@@ -7,8 +7,9 @@ Mirrors the Python API the reference's hot path exposes (deepinteract_modules.py
   and edata['f'] [E,128] (the last intermediate layer's edges) in place, keeps batch_num_*.
 * ``LitGINI`` (:1478): ``gnn_forward`` (:1660-1679), ``shared_step`` (:1687-1745),
   ``predict_step`` (:2178-2184), ``test_step`` (:2018-2101), plus ``predict_batch`` (the batched
-  entry the benchmark and the distributed driver use) and ``predict_contacts`` (the same with each
-  complex's ranked contacts).
+  entry the benchmark and the distributed driver use), ``predict_contacts`` (the same with each
+  complex's ranked contacts), ``test_batch`` (test_step's figures for many complexes at once) and
+  ``test_epoch_end`` (:2103-2165, the medians and the top-k CSV).
 
 Graphs may be ``deepinteract_amd.graph.ResidueGraph`` or real ``dgl.DGLGraph`` objects.
 Batched graphs get per-chain semantics (each chain as the reference computes it at batch size 1).
@@ -24,7 +25,8 @@ from .config import GeoTConfig, NODE_COUNT_LIMIT, RESIDUE_COUNT_LIMIT
 from .engine import GeoTEngine, HeadPrologueOp, PairTensorOp, gpu_device
 from .graph import GraphBatch, ResidueGraph, batch as batch_graphs, unbatch
 from .head import HeadNormOps, ResNet2DInputWithOptAttention, contact_probs
-from .ranking import ContactAucOp, ContactRankOp, confusion_metrics, labels_from_examples, topk_metrics
+from .ranking import (ContactAucOp, ContactRankOp, confusion_metrics, labels_from_examples,
+                      labels_from_examples_batch, topk_metrics)
 
 
 def _identity_embedding_sd(sd, cfg: GeoTConfig):
@@ -329,6 +331,83 @@ class LitGINI(nn.Module):
         out["confusion"] = confusion
         out["test_auroc"], out["test_auprc"] = auc.auroc, auc.auprc
         out.update(confusion_metrics(**confusion))
+        return out
+
+    def test_batch(self, gb: GraphBatch, pairs, examples_list, filepaths, keep_maps=None):
+        """test_step for many complexes at once: one forward (``_forward_batch``), one batched ranking
+        call and one batched AUC call (ranking.ContactRankOp.batch / ContactAucOp.batch), whatever
+        the number of complexes. pairs as in ``predict_batch``; examples_list[i] / filepaths[i] belong
+        to complex i.
+
+        Returns one dict per complex with exactly test_step's keys, every figure that complex's own:
+        loss (its mean cross-entropy), the six top_* figures, confusion, test_auroc / test_auprc,
+        test_acc .. test_f1 from its confusion counts, target. test_preds / test_preds_rounded /
+        test_labels are copied to the host only for the first ``keep_maps`` complexes (None: all; the
+        reference keeps 55 of an epoch); the other dicts hold None there. The host reads the device
+        once for the labels' validation, once per metrics table and once for all top_hits."""
+        import os
+        if not (len(pairs) == len(examples_list) == len(filepaths)):
+            raise ValueError("test_batch: one examples tensor and one file path per complex")
+        logits_list, _, _ = self._forward_batch(gb, pairs)
+        rank, auc_op = self._ranker(), self._auc()
+        shapes = [(int(lg.shape[2]), int(lg.shape[3])) for lg in logits_list]
+        labels = labels_from_examples_batch([ex.to(rank.device) for ex in examples_list], shapes)
+        ranks = rank.batch([lg.contiguous() for lg in logits_list], labels_list=labels,
+                           threshold=self.pos_prob_threshold)
+        aucs = auc_op.batch([r.probs for r in ranks], labels)   # the maps the ranking judged
+        hits = ranks.hits.cpu()
+        keep = len(ranks) if keep_maps is None else int(keep_maps)
+        outs = []
+        for i, (r, a, (l1, l2)) in enumerate(zip(ranks, aucs, shapes)):
+            k = min(l1, l2)
+            confusion = {f: getattr(r, f) for f in ("tp", "fp", "fn", "tn")}
+            out = {"loss": r.ce_sum / (l1 * l2)}
+            out.update(topk_metrics(hits[ranks.hits_off[i]:ranks.hits_off[i] + k], r.num_pos, k))
+            if i < keep:
+                out["test_preds"] = r.probs.cpu().numpy()
+                out["test_preds_rounded"] = (r.probs >= self.pos_prob_threshold).float().cpu().numpy()
+                out["test_labels"] = labels[i].view(l1, l2).float().cpu().numpy()
+            else:
+                out["test_preds"] = out["test_preds_rounded"] = out["test_labels"] = None
+            out["target"] = str(filepaths[i]).split(os.sep)[-1][:4]
+            out["confusion"] = confusion
+            out["test_auroc"], out["test_auprc"] = a.auroc, a.auprc
+            out.update(confusion_metrics(**confusion))
+            outs.append(out)
+        return outs
+
+    _MEDIANS = ("test_acc", "test_prec", "test_recall", "test_f1", "test_auroc", "test_auprc")
+    _CSV_COLUMNS = ("top_10_prec", "top_l_by_10_prec", "top_l_by_5_prec", "top_l_recall", "top_l_by_2_recall",
+                    "top_l_by_5_recall", "target")
+
+    def test_epoch_end(self, outputs, csv_path=None, group=None):
+        """LitGINI.test_epoch_end (deepinteract_modules.py:2103-2165) without the loggers. outputs: the
+        dicts of test_step / test_batch of this rank.
+
+        Returns med_test_acc / prec / recall / f1 / auroc / auprc: ``torch.median`` over all complexes
+        (the lower middle value of an even count; NaN if any value is NaN). With a process ``group``
+        every rank's per-complex values are all-gathered first (ranks may hold different counts), so
+        every rank returns the medians of all of them. With ``csv_path`` the six top-k columns plus
+        ``target`` are written, one row per complex of THIS rank's outputs, in the layout
+        ``DataFrame.to_csv`` writes (a leading unnamed index column; NaN as an empty field)."""
+        vals = [[float(o[name]) for name in self._MEDIANS] for o in outputs]
+        if group is not None:
+            import torch.distributed as dist
+            gathered = [None] * dist.get_world_size(group)
+            dist.all_gather_object(gathered, vals, group=group)
+            vals = [row for part in gathered for row in part]
+        if not vals:
+            raise ValueError("test_epoch_end: no outputs")
+        table = torch.tensor(vals, dtype=torch.float64)
+        out = {"med_" + name: float(torch.median(table[:, c])) for c, name in enumerate(self._MEDIANS)}
+        if csv_path is not None:
+            import csv
+            with open(csv_path, "w", newline="") as fh:
+                wr = csv.writer(fh, lineterminator="\n")
+                wr.writerow(("",) + self._CSV_COLUMNS)
+                for i, o in enumerate(outputs):
+                    row = [o[c] for c in self._CSV_COLUMNS]
+                    wr.writerow([i] + ["" if isinstance(v, float) and v != v else v for v in row])
         return out
 
 

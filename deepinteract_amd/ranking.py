@@ -18,6 +18,11 @@ mode and scikit-learn compute) from that stored map and its labels, again withou
 negatives over the gaps between them determine both. ``confusion_metrics`` restates torchmetrics'
 test_acc / test_prec / test_recall / test_f1 from ``tp, fp, fn, tn``.
 
+``ContactRankOp.batch`` / ``ContactAucOp.batch`` run either op over many complexes of different shapes
+with one launch sequence (``di_contact_rank_batch`` / ``di_contact_auc_batch``) and give every complex
+the bits of the single call; ``labels_from_examples_batch`` validates a batch's labels with one host
+read.
+
 Out of scope: sending top-k lists instead of maps through ``predict_sharded``.
 """
 from __future__ import annotations
@@ -30,19 +35,43 @@ from . import _lib
 from .engine import _ptr, _stream, check_on, gpu_device
 
 
+class _MetricsTable:
+    """The metrics records of one batch, [count, words] int64 on the device: read with one copy (which
+    waits for the stream the batch ran on) when the first result asks for a number."""
+
+    def __init__(self, dev):
+        self.dev, self._host = dev, None
+
+    def row(self, i: int) -> bytes:
+        if self._host is None:
+            self._host = self.dev.cpu().numpy()
+        return self._host[i].tobytes()
+
+
+class ContactRankingBatch(list):
+    """``ContactRankOp.batch``'s list of ``ContactRanking``, plus the packed buffers its elements are
+    views of: ``hits`` (all complexes' top_hits, int32; None without labels) and ``hits_off`` (complex
+    i's start in it), so that a caller can bring every complex's hits to the host with one copy."""
+
+    hits = None
+    hits_off = ()
+
+
 class ContactRanking:
     """Result of one ``ContactRankOp`` call (device tensors; label fields None without labels).
 
     probs [L1, L2] fp32; ids [K] int32 flat indices in rank order; pairs [K, 2] their (i, j);
     scores [K] fp32; hits [K] int32, hits[r] = positives among ranks 0..r. ``num_pos, tp, fp, fn,
     tn, ce_sum`` are host numbers, read from the device on first use with one copy (which waits for
-    the stream the op ran on)."""
+    the stream the op ran on); the results of one ``batch`` call share that copy (``table``, ``index``:
+    the batch's metrics table and this complex's row)."""
 
     _FIELDS = tuple(f for f, _ in _lib.DiRankMetrics._fields_)
 
-    def __init__(self, probs, ids, scores, hits, metrics_dev, l2):
+    def __init__(self, probs, ids, scores, hits, metrics_dev, l2, table=None, index=0):
         self.probs, self.ids, self.scores, self.hits = probs, ids, scores, hits
         self._metrics_dev, self._metrics, self._l2 = metrics_dev, None, l2
+        self._table, self._index = table, index
 
     @property
     def pairs(self):
@@ -53,7 +82,7 @@ class ContactRanking:
         if self._metrics_dev is None:
             raise ValueError("the ranking was computed without labels")
         if self._metrics is None:
-            raw = self._metrics_dev.cpu().numpy().tobytes()
+            raw = self._metrics_dev.cpu().numpy().tobytes() if self._table is None else self._table.row(self._index)
             m = _lib.DiRankMetrics.from_buffer_copy(raw)
             self._metrics = {f: getattr(m, f) for f in self._FIELDS}
         return self._metrics
@@ -84,7 +113,8 @@ class ContactRankOp:
             self._work = torch.empty((nb + 7) // 8, dtype=torch.int64, device=self.device)
         return self._work
 
-    def __call__(self, logits, k=None, labels=None, threshold=0.5, probs_out=None):
+    def _check(self, logits, k, labels):
+        """The argument checks of one complex: (dtype code, l1, l2, k)."""
         if logits.dim() != 4 or logits.shape[0] != 1 or logits.shape[1] != 2 or not logits.is_contiguous():
             raise ValueError("contact ranking takes one contiguous [1, 2, L1, L2] logits tensor")
         if logits.dtype == torch.float32:
@@ -96,10 +126,16 @@ class ContactRankOp:
         l1, l2 = int(logits.shape[2]), int(logits.shape[3])
         n = l1 * l2
         k = min(l1, l2) if k is None else int(k)
-        check_on(self.device, "ContactRankOp", logits, labels, probs_out)
+        check_on(self.device, "ContactRankOp", logits, labels)
         if labels is not None:
             if labels.dtype != torch.uint8 or labels.numel() != n or not labels.is_contiguous():
                 raise ValueError("labels: a contiguous uint8 tensor of L1 * L2 elements")
+        return dt, l1, l2, k
+
+    def __call__(self, logits, k=None, labels=None, threshold=0.5, probs_out=None):
+        dt, l1, l2, k = self._check(logits, k, labels)
+        n = l1 * l2
+        check_on(self.device, "ContactRankOp", probs_out)
         if probs_out is None:
             probs = torch.empty(l1, l2, dtype=torch.float32, device=self.device)
         else:
@@ -118,6 +154,85 @@ class ContactRankOp:
                                             _ptr(work), _stream()), "di_contact_rank")
         return ContactRanking(probs, ids, scores, hits, metrics, l2)
 
+    def batch(self, logits_list, k=None, labels_list=None, threshold=0.5):
+        """The op over many complexes of different shapes with ONE launch sequence per DI_BATCH_MAX
+        complexes (``di_contact_rank_batch``): a ``ContactRankingBatch`` (a list) of ``ContactRanking``,
+        each with the bits the single call gives on the same inputs. logits_list: [1, 2, L1, L2]
+        tensors of one dtype (mixed: TypeError); k: None (min(L1, L2) per complex), one int, or one
+        per complex; labels_list: None, or one uint8 label tensor per complex. The argument checks are
+        the single op's, applied to every element. The outputs are views of packed buffers (one
+        allocation per kind; every map starts 16-B aligned); the descriptor table goes to the device
+        with one pinned, non-blocking copy on the current stream; the results share one metrics
+        table, read from the device once, on first use."""
+        count = len(logits_list)
+        if count < 1:
+            raise ValueError("contact ranking: an empty batch")
+        ks = list(k) if isinstance(k, (list, tuple)) else [k] * count
+        if labels_list is not None and len(labels_list) != count or len(ks) != count:
+            raise ValueError("contact ranking: one k and one labels tensor per complex")
+        with_labels = labels_list is not None
+        checked = [self._check(lg, ks[i], labels_list[i] if with_labels else None) for i, lg in enumerate(logits_list)]
+        if any(c[0] != checked[0][0] for c in checked):
+            raise TypeError("contact ranking: one batch takes logits of one dtype")
+        dt = checked[0][0]
+        for _, l1, l2, kk in checked:   # sizes only: raises as the single op does
+            if self.lib.di_contact_rank_work_bytes(l1 * l2, kk) < 0:
+                self._workspace(l1 * l2, kk)
+        map_off, k_off, at_map, at_k = [], [], 0, 0
+        for _, l1, l2, kk in checked:
+            map_off.append(at_map)
+            k_off.append(at_k)
+            at_map += (l1 * l2 + 3) // 4 * 4
+            at_k += kk
+        dev = self.device
+        probs = torch.empty(at_map, dtype=torch.float32, device=dev)
+        ids = torch.empty(at_k, dtype=torch.int32, device=dev)
+        scores = torch.empty(at_k, dtype=torch.float32, device=dev)
+        words = ctypes.sizeof(_lib.DiRankMetrics) // 8
+        hits = torch.empty(at_k, dtype=torch.int32, device=dev) if with_labels else None
+        metrics = torch.empty(count, words, dtype=torch.int64, device=dev) if with_labels else None
+        table = _MetricsTable(metrics) if with_labels else None
+        out = ContactRankingBatch()
+        out.hits, out.hits_off = hits, tuple(k_off)
+        items = (_lib.DiRankItem * count)()
+        for i, (lg, (_, l1, l2, kk)) in enumerate(zip(logits_list, checked)):
+            n = l1 * l2
+            r = ContactRanking(probs[map_off[i]:map_off[i] + n].view(l1, l2), ids[k_off[i]:k_off[i] + kk],
+                               scores[k_off[i]:k_off[i] + kk], hits[k_off[i]:k_off[i] + kk] if with_labels else None,
+                               metrics[i] if with_labels else None, l2, table, i)
+            out.append(r)
+            it = items[i]
+            it.logits, it.probs, it.top_ids, it.top_scores = (t.data_ptr() for t in (lg, r.probs, r.ids, r.scores))
+            if with_labels:
+                it.labels, it.top_hits, it.metrics = labels_list[i].data_ptr(), r.hits.data_ptr(), metrics[i].data_ptr()
+            it.l1, it.l2, it.k = l1, l2, kk
+        for lo in range(0, count, _lib.DI_BATCH_MAX):
+            m = min(_lib.DI_BATCH_MAX, count - lo)
+            part = (_lib.DiRankItem * m).from_buffer(items, lo * ctypes.sizeof(_lib.DiRankItem))
+            nb = self.lib.di_contact_rank_batch_work_bytes(part, m)
+            if nb < 0:
+                raise ValueError(f"contact ranking of a batch of {m}: code {nb}")
+            work, part_dev = _grow(self, nb), _table_to_device(part, dev)
+            _lib.check(self.lib.di_contact_rank_batch(dt, part, _ptr(part_dev), m, ctypes.c_float(threshold),
+                                                      _ptr(work), _stream()), "di_contact_rank_batch")
+        return out
+
+
+def _grow(op, nbytes):
+    """The op's workspace, grown to nbytes (shared by its single and batched calls: stream order)."""
+    if op._work is None or op._work.numel() * 8 < nbytes:
+        op._work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=op.device)
+    return op._work
+
+
+def _table_to_device(items, device):
+    """A ctypes array of descriptors as a device tensor: staged in a fresh pinned buffer (the host
+    allocator keeps it until the copy has run) and copied without blocking on the current stream."""
+    nbytes = ctypes.sizeof(items)
+    pinned = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+    ctypes.memmove(pinned.data_ptr(), ctypes.addressof(items), nbytes)
+    return pinned.to(device, non_blocking=True)
+
 
 class ContactAuc:
     """Result of one ``ContactAucOp`` call. ``num_pos, num_neg, num_nan, pos_distinct, u2, auroc,
@@ -125,15 +240,19 @@ class ContactAuc:
     for the stream the op ran on). u2 = sum over (positive, negative) pairs of 2 [p_pos > p_neg] +
     [p_pos == p_neg]; auroc = u2 / (2 num_pos num_neg); both figures are float('nan') when a class is
     empty or a score is NaN (then u2 = pos_distinct = 0). ``rerun(num_pos)``, if given, runs the op
-    again with room for every positive: used once, on that first read, if this run overflowed."""
+    again with room for every positive: used once, on that first read, if this run overflowed. The
+    results of one ``batch`` call share one copy of their records (``table``, ``index``: the batch's
+    metrics table and this complex's row); one that overflowed is rerun alone."""
 
     _FIELDS = tuple(f for f, _ in _lib.DiAucMetrics._fields_ if f != "pad")
 
-    def __init__(self, metrics_dev, max_pos, rerun=None):
+    def __init__(self, metrics_dev, max_pos, rerun=None, table=None, index=0):
         self._metrics_dev, self._metrics, self.max_pos, self._rerun = metrics_dev, None, max_pos, rerun
+        self._table, self._index = table, index
 
     def _read(self) -> dict:
-        m = _lib.DiAucMetrics.from_buffer_copy(self._metrics_dev.cpu().numpy().tobytes())
+        raw = self._metrics_dev.cpu().numpy().tobytes() if self._table is None else self._table.row(self._index)
+        m = _lib.DiAucMetrics.from_buffer_copy(raw)
         return {f: getattr(m, f) for f in self._FIELDS}
 
     def metrics(self) -> dict:
@@ -141,7 +260,7 @@ class ContactAuc:
             m = self._read()
             if m["overflow"] and self._rerun is not None:
                 again = self._rerun(m["num_pos"])
-                self._metrics_dev, self.max_pos = again._metrics_dev, again.max_pos
+                self._metrics_dev, self.max_pos, self._table = again._metrics_dev, again.max_pos, None
                 m = self._read()
             self._metrics, self._rerun = m, None
         return self._metrics
@@ -212,6 +331,49 @@ class ContactAucOp:
         res._rerun = lambda num_pos: self._run(probs, labels, num_pos)   # keeps probs and labels alive
         return res
 
+    def batch(self, probs_list, labels_list, max_pos=None):
+        """The op over many complexes of different shapes with ONE launch sequence per DI_BATCH_MAX
+        complexes (``di_contact_auc_batch``): a list of ``ContactAuc``, each with the bits the single
+        call gives on the same inputs. max_pos: None (the default per complex), one int, or one per
+        complex. The argument checks are the single op's, applied to every element. The descriptor
+        table goes to the device with one pinned, non-blocking copy on the current stream; the results
+        share one metrics table, read from the device once, on first use; a complex that overflowed
+        its max_pos is rerun alone through the single op on that read, and leaves its neighbours'
+        figures as they are."""
+        count = len(probs_list)
+        if count < 1:
+            raise ValueError("contact AUC: an empty batch")
+        mps = list(max_pos) if isinstance(max_pos, (list, tuple)) else [max_pos] * count
+        if len(labels_list) != count or len(mps) != count:
+            raise ValueError("contact AUC: one labels tensor and one max_pos per complex")
+        for i in range(count):
+            mps[i] = self.check_args(probs_list[i], labels_list[i], mps[i])
+            check_on(self.device, "ContactAucOp", probs_list[i], labels_list[i])
+            if self.lib.di_contact_auc_work_bytes(probs_list[i].numel(), mps[i]) < 0:
+                self._workspace(probs_list[i].numel(), mps[i])    # raises as the single op does
+        words = ctypes.sizeof(_lib.DiAucMetrics) // 8
+        metrics = torch.empty(count, words, dtype=torch.int64, device=self.device)
+        table = _MetricsTable(metrics)
+        items = (_lib.DiAucItem * count)()
+        out = []
+        for i, (probs, labels) in enumerate(zip(probs_list, labels_list)):
+            it = items[i]
+            it.probs, it.labels, it.out = probs.data_ptr(), labels.data_ptr(), metrics[i].data_ptr()
+            it.n, it.max_pos = probs.numel(), mps[i]
+            res = ContactAuc(metrics[i], mps[i], None, table, i)
+            res._rerun = lambda num_pos, p=probs, y=labels: self._run(p, y, num_pos)   # keeps both alive
+            out.append(res)
+        for lo in range(0, count, _lib.DI_BATCH_MAX):
+            m = min(_lib.DI_BATCH_MAX, count - lo)
+            part = (_lib.DiAucItem * m).from_buffer(items, lo * ctypes.sizeof(_lib.DiAucItem))
+            nb = self.lib.di_contact_auc_batch_work_bytes(part, m)
+            if nb < 0:
+                raise ValueError(f"contact AUC of a batch of {m}: code {nb}")
+            work, part_dev = _grow(self, nb), _table_to_device(part, self.device)
+            _lib.check(self.lib.di_contact_auc_batch(part, _ptr(part_dev), m, _ptr(work), _stream()),
+                       "di_contact_auc_batch")
+        return out
+
 
 def confusion_metrics(tp, fp, fn, tn) -> dict:
     """test_acc / test_prec / test_recall / test_f1 of LitGINI.test_step from the confusion counts at
@@ -255,6 +417,43 @@ def labels_from_examples(examples, l1: int, l2: int):
     return out
 
 
+def labels_from_examples_batch(examples_list, shapes):
+    """``labels_from_examples`` for many complexes: shapes[i] = (l1, l2) of examples_list[i]. The same
+    validation and the same result per complex, with ONE host read for the whole batch (the single
+    function reads the device three times per complex)."""
+    if len(examples_list) != len(shapes):
+        raise ValueError("examples: one (l1, l2) per complex")
+    flags, outs = [], []
+    for examples, (l1, l2) in zip(examples_list, shapes):
+        if examples.dim() != 2 or examples.shape[1] != 3:
+            raise ValueError("examples: [n, 3] rows of (i, j, label)")
+        n = l1 * l2
+        if examples.shape[0] != n:
+            raise ValueError(f"examples: {examples.shape[0]} rows for {l1} x {l2} = {n} pairs "
+                             "(every pair exactly once)")
+        ex = examples.to(torch.int64)
+        i, j, lab = ex[:, 0], ex[:, 1], ex[:, 2]
+        outside = (i < 0) | (i >= l1) | (j < 0) | (j >= l2)
+        flat = torch.where(outside, torch.zeros_like(i), i * l2 + j)    # a bad row scatters nowhere new
+        seen = torch.zeros(n, dtype=torch.int32, device=examples.device)
+        seen.index_add_(0, flat, torch.ones(n, dtype=torch.int32, device=examples.device))
+        flags.append(torch.stack((outside.any(), ((lab != 0) & (lab != 1)).any(), (seen != 1).any())))
+        out = torch.zeros(n, dtype=torch.uint8, device=examples.device)
+        out[flat] = lab.to(torch.uint8)
+        outs.append(out)
+    if flags:
+        devices = {f.device for f in flags}
+        host = (torch.stack(flags) if len(devices) == 1 else torch.stack([f.cpu() for f in flags])).cpu()
+        for bad in host.tolist():
+            if bad[0]:
+                raise ValueError("examples: a pair index outside the complex")
+            if bad[1]:
+                raise ValueError("examples: labels must be 0 or 1")
+            if bad[2]:
+                raise ValueError("examples: a pair is missing or listed twice")
+    return outs
+
+
 def topk_metrics(hits, num_pos, l: int) -> dict:
     """The six top-k figures of LitGINI.test_step from ``hits`` (hits[r] = positives among ranks
     0..r; a tensor, array or list) with the reference's arithmetic (deepinteract_utils.py:977-995):
@@ -282,5 +481,5 @@ def topk_metrics(hits, num_pos, l: int) -> dict:
             "top_l_recall": recall(l), "top_l_by_2_recall": recall(l // 2), "top_l_by_5_recall": recall(l // 5)}
 
 
-__all__ = ["ContactRankOp", "ContactRanking", "ContactAucOp", "ContactAuc", "confusion_metrics",
-           "labels_from_examples", "topk_metrics"]
+__all__ = ["ContactRankOp", "ContactRanking", "ContactRankingBatch", "ContactAucOp", "ContactAuc",
+           "confusion_metrics", "labels_from_examples", "labels_from_examples_batch", "topk_metrics"]

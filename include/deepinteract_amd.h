@@ -35,6 +35,7 @@
  *                                                                    deepinteract_utils.py:977-995
  *   di_contact_auc   test_step's exact per-complex test_auroc / test_auprc (class 1)
  *                                                                    deepinteract_modules.py:2018-2101
+ *   di_contact_rank_batch / di_contact_auc_batch  both over many complexes in one launch sequence
  *
  * Module-at-a-time entry points (deepinteract_amd/layers.py; same math as the fused kernels):
  *   di_conformation   ConformationModule.forward                      deepinteract_modules.py:373-455
@@ -410,6 +411,53 @@ typedef struct {
 int64_t di_contact_auc_work_bytes(int64_t n, int64_t max_pos);
 int di_contact_auc(const float* probs, const uint8_t* labels, int64_t n, int64_t max_pos,
                    di_auc_metrics* out, void* work, void* stream);
+
+/* ---- both of the above over a ragged batch (an addition to ABI 8) ---------------------------
+ * `count` complexes of different shapes in ONE launch sequence, whatever count is: one memset + 6
+ * launches (rank), one memset + 19 launches (AUC). One item per complex holds the single call's
+ * arguments. The grid's y index names the complex; a block reads its item from the DEVICE copy of the
+ * table and derives its geometry from that complex's sizes alone, by the single call's functions, so
+ * every output of a complex has the bits the single call gives on the same inputs (ce_sum, auroc and
+ * auprc included), whatever its neighbours hold.
+ *   items      host array [count]: validated, and used for grid sizes and offsets; may be freed on
+ *              return
+ *   items_dev  a copy of it in device memory, made by the caller (in stream order before the call;
+ *              it must stay unchanged until the call's kernels have run)
+ * hdr_off / work_off: the complex's places in `work`, filled by the *_batch_work_bytes call (16-B
+ * aligned; all that the call clears lies contiguous at the front: every complex's header, for the AUC
+ * with its bins); the batch call refuses other values. work: that many bytes, 16-B aligned.
+ * One dtype and one threshold serve a rank batch, and its items carry labels / top_hits / metrics
+ * either all or none. The AUC overflow rule holds per complex (overflow = 1, only the three counts
+ * valid), and leaves the neighbours alone.
+ * Asynchronous, no allocation, every refusal before any launch. DI_EINVAL: count < 1, a NULL table,
+ * offsets that the helper did not fill, or any item the single call refuses with DI_EINVAL;
+ * DI_ERANGE: count > DI_BATCH_MAX, or an item the single call refuses with DI_ERANGE. The
+ * *_batch_work_bytes helpers return the same codes for the sizes. */
+#define DI_BATCH_MAX 1024
+typedef struct {
+  const void* logits;
+  const uint8_t* labels;
+  float* probs;
+  int32_t* top_ids;
+  float* top_scores;
+  int32_t* top_hits;
+  di_rank_metrics* metrics;
+  int64_t hdr_off, work_off;
+  int32_t l1, l2, k, pad;
+} di_rank_item;
+typedef struct {
+  const float* probs;
+  const uint8_t* labels;
+  di_auc_metrics* out;
+  int64_t n, max_pos;
+  int64_t hdr_off, work_off;
+} di_auc_item;
+int64_t di_contact_rank_batch_work_bytes(di_rank_item* items, int32_t count);
+int di_contact_rank_batch(int32_t dtype, const di_rank_item* items, const di_rank_item* items_dev,
+                          int32_t count, float threshold, void* work, void* stream);
+int64_t di_contact_auc_batch_work_bytes(di_auc_item* items, int32_t count);
+int di_contact_auc_batch(const di_auc_item* items, const di_auc_item* items_dev, int32_t count,
+                         void* work, void* stream);
 
 /* ---- graph builder ----------------------------------------------------------------------- */
 /* Cα kNN per chain: idx_out [Nt,k] chain-local neighbour ids (ascending squared distance,
