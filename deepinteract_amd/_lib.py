@@ -78,6 +78,14 @@ class DiAucItem(ctypes.Structure):
                 ("work_off", ctypes.c_int64)]
 
 
+class DiHeadConvArgs(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("in_scale", ctypes.c_void_p),
+                ("in_shift", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("y", ctypes.c_void_p),
+                ("stats", ctypes.c_void_p), ("cin", ctypes.c_int32), ("cout", ctypes.c_int32),
+                ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("ksize", ctypes.c_int32),
+                ("dilation", ctypes.c_int32), ("in_elu", ctypes.c_int32)]
+
+
 # pair-queue words (include/deepinteract_amd.h, di_pair_queue_bytes)
 PQ_READY, PQ_ERROR, PQ_GAVE_UP, PQ_SBYTES, PQ_HBYTES = 0, 32, 33, 40, 42
 
@@ -122,6 +130,11 @@ _SIGS = {
     "di_inorm_work_bytes": ([_I, ctypes.c_int64], ctypes.c_int64),
     "di_se_scale_add": ([_I, _P, _P, _P, _P, _I, ctypes.c_int64, _P, _P], ctypes.c_int),
     "di_channel_mean": ([_I, _P, _I, ctypes.c_int64, _P, _P, _P, _P], ctypes.c_int),
+    "di_head_conv": ([_I, ctypes.POINTER(DiHeadConvArgs), _P], ctypes.c_int),
+    "di_head_conv_check": ([_I, ctypes.POINTER(DiHeadConvArgs)], ctypes.c_int),
+    "di_head_conv_stats_bytes": ([_I, _I, _I], ctypes.c_int64),
+    "di_plane_stats": ([_I, _P, _I, ctypes.c_int64, _P, _P], ctypes.c_int),
+    "di_head_norm_fold": ([_P, _I, ctypes.c_int64, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P], ctypes.c_int),
     "di_contact_rank_work_bytes": ([ctypes.c_int64, _I], ctypes.c_int64),
     "di_contact_rank": ([_I, _P, _I, _I, _I, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
     "di_contact_auc_work_bytes": ([ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),

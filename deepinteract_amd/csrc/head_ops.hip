@@ -1,4 +1,4 @@
-// Contact-head body ops: the dilated-ResNet head stays on PyTorch-ROCm for its
+// Contact-head body ops: by default the dilated-ResNet head stays on PyTorch-ROCm for its
 // convolutions (MIOpen / hipBLASLt), but its HBM-bound normalisation passes are fused here.
 //
 //  * di_inorm_elu: y = ELU(InstanceNorm2d(x)) for one [C, HW] image (batch 1, NCHW), the
@@ -14,6 +14,10 @@
 //  * di_se_scale_add: y = (x + b[c]) * s[c] + res — the block's last conv bias, SEBlock's channel
 //    gate (:954-970) and the residual add (:1095): 3 plane passes instead of 7.
 //  * di_channel_mean: SEBlock's x.mean(dim=(2, 3)) (+ the deferred conv bias), one read pass.
+//  * di_plane_stats / di_head_norm_fold (with the HIP convolutions, head_conv.hip): the statistics pass
+//    alone, into a self-describing buffer, and the fold of such a buffer -- written by this pass or by
+//    a convolution's epilogue -- into the per-channel scale / shift the next convolution applies as it
+//    loads, or into the SE squeeze.
 // The convs before an InstanceNorm run without their bias (a per-channel constant cancels in
 // the normalisation exactly), so the head does no separate bias-add passes.
 // fp32 accumulation everywhere, fp64 for the statistics; bf16 storage rounds once (RNE).
@@ -98,9 +102,14 @@ struct Plane {
 
 template <typename T>
 __global__ __launch_bounds__(HO_THREADS) void k_inorm_stats(const T* __restrict__ x, int64_t hw,
-                                                            double* __restrict__ part) {
+                                                            double* __restrict__ part,
+                                                            int64_t* __restrict__ hdr = nullptr) {
   using V = Vec<T>;
   const int c = blockIdx.y, split = gridDim.x;
+  if (hdr && c == 0 && blockIdx.x == 0 && threadIdx.x == 0) {  // di_plane_stats: partials per channel
+    hdr[0] = split;
+    hdr[1] = 0;
+  }
   const Plane P(hw, V::N, c, split, blockIdx.x);
   double s = 0.0, ss = 0.0;
   for (int64_t i = P.lo + threadIdx.x; i < P.hi; i += HO_THREADS) {
@@ -236,6 +245,45 @@ __global__ void k_channel_mean(const double* __restrict__ part, int split, int c
   mean[c] = (float)(a / (double)hw + (bias ? (double)bias[c] : 0.0));
 }
 
+// One block per channel adds the channel's n partials (n from the buffer's header) in a fixed order
+// -- thread t takes partials t, t + 256, ..., then a tree over the threads -- and derives, in fp64,
+// mean, biased variance, scale = gamma / sqrt(var + eps), shift = beta - mean * scale.
+__global__ __launch_bounds__(HO_THREADS) void k_head_norm_fold(const double* __restrict__ stats, int64_t hw,
+                                                               const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, float eps,
+                                                               const float* __restrict__ bias,
+                                                               float* __restrict__ scale, float* __restrict__ shift,
+                                                               float* __restrict__ mean) {
+  const int c = blockIdx.x;
+  const int64_t n = reinterpret_cast<const int64_t*>(stats)[0];
+  const double* part = stats + 2 + (int64_t)c * n * 2;
+  double a = 0.0, b = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += HO_THREADS) {
+    a += part[2 * i];
+    b += part[2 * i + 1];
+  }
+  __shared__ double red[2][HO_THREADS];
+  red[0][threadIdx.x] = a;
+  red[1][threadIdx.x] = b;
+  __syncthreads();
+  for (int s = HO_THREADS / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + s];
+      red[1][threadIdx.x] += red[1][threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double m = red[0][0] / (double)hw;
+    double var = red[1][0] / (double)hw - m * m;  // biased, as InstanceNorm2d
+    var = var > 0.0 ? var : 0.0;
+    const double sc = (gamma ? (double)gamma[c] : 1.0) / sqrt(var + (double)eps);
+    if (scale) scale[c] = (float)sc;
+    if (shift) shift[c] = (float)((beta ? (double)beta[c] : 0.0) - m * sc);
+    if (mean) mean[c] = (float)(m + (bias ? (double)bias[c] : 0.0));
+  }
+}
+
 // blocks per channel: fill the chip (>= ~2048 blocks) without slices under 2 vectors per thread
 static int ho_split(int channels, int64_t hw, int vec) {
   int split = (2048 + channels - 1) / channels;
@@ -308,6 +356,32 @@ extern "C" int di_se_scale_add(di_dtype dt, const void* x, const float* scale, c
   else
     hipLaunchKernelGGL(k_se_scale_add<float>, grid, dim3(HO_THREADS), 0, s, (const float*)x, scale, bias,
                        (const float*)res, hw, (float*)y);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DI_OK : (int)e;
+}
+
+extern "C" int di_plane_stats(di_dtype dt, const void* x, int32_t channels, int64_t hw, void* stats, void* stream) {
+  if (!x || !stats || channels <= 0 || channels > 65535 || hw <= 0) return DI_EINVAL;
+  if ((dt != DI_F32 && dt != DI_BF16) || !aligned16(x) || ((uintptr_t)stats & 7) != 0) return DI_EINVAL;
+  const dim3 grid(ho_split(channels, hw, dt == DI_BF16 ? 8 : 4), channels);
+  hipStream_t s = (hipStream_t)stream;
+  int64_t* hdr = reinterpret_cast<int64_t*>(stats);
+  double* part = reinterpret_cast<double*>(stats) + 2;
+  if (dt == DI_BF16)
+    hipLaunchKernelGGL(k_inorm_stats<u16>, grid, dim3(HO_THREADS), 0, s, (const u16*)x, hw, part, hdr);
+  else
+    hipLaunchKernelGGL(k_inorm_stats<float>, grid, dim3(HO_THREADS), 0, s, (const float*)x, hw, part, hdr);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DI_OK : (int)e;
+}
+
+extern "C" int di_head_norm_fold(const void* stats, int32_t channels, int64_t hw, const float* gamma,
+                                 const float* beta, float eps, const float* bias, float* scale, float* shift,
+                                 float* mean, void* stream) {
+  if (!stats || ((uintptr_t)stats & 7) != 0 || channels <= 0 || channels > 65535 || hw <= 0) return DI_EINVAL;
+  if (!(eps >= 0.f)) return DI_EINVAL;
+  hipLaunchKernelGGL(k_head_norm_fold, dim3(channels), dim3(HO_THREADS), 0, (hipStream_t)stream,
+                     (const double*)stats, hw, gamma, beta, eps, bias, scale, shift, mean);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
 }

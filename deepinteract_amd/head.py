@@ -1,5 +1,5 @@
-"""Dilated-ResNet contact head — stays on PyTorch-ROCm (MIOpen convolutions), as north_star
-specifies. Module/parameter names match the reference's ``interact_module`` so reference
+"""Dilated-ResNet contact head — on PyTorch-ROCm (MIOpen convolutions) by default, as north_star
+specifies; opt-in, the bf16 head's convolutions run on HIP (HeadConvOps, csrc/head_conv.hip). Module/parameter names match the reference's ``interact_module`` so reference
 state dicts load unchanged: ResNet2DInputWithOptAttention (deepinteract_modules.py:1155-1248),
 ResNet (:973-1106), SEBlock (:954-970). The optional regional attention (MHA2D) is not part
 of the default model (``use_interact_attention=False``) and is not implemented.
@@ -103,6 +103,85 @@ class HeadNormOps:
         return y
 
 
+class HeadConvOps:
+    """The head's convolutions on HIP (csrc/head_conv.hip): 1x1 and dilated 3x3 on the matrix cores,
+    bf16 NCHW, with the InstanceNorm + ELU in front of a convolution applied as it loads its input
+    (``ELU(x * scale + shift)``) and the next norm's statistics left by its epilogue. One
+    [1, C, H, W] contiguous bf16 GPU image per call. No CPU fallback: constructing it without the
+    HIP library / a GPU raises."""
+
+    def __init__(self, device):
+        from . import _lib
+        if not torch.cuda.is_available():
+            raise RuntimeError("HeadConvOps needs a ROCm GPU (no CPU fallback)")
+        self._lib = _lib
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        self._stats = None
+
+    @staticmethod
+    def _check(x):
+        if x.dim() != 4 or x.shape[0] != 1 or not x.is_contiguous() or not x.is_cuda or x.dtype != torch.bfloat16:
+            raise ValueError("head convolutions take one contiguous NCHW [1, C, H, W] bf16 GPU image")
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    @staticmethod
+    def _ptr(t):
+        return ctypes.c_void_p(0 if t is None else t.data_ptr())
+
+    def stats_buffer(self, C, H, W, device):
+        """The statistics buffer the next conv / plane_stats writes and the next fold reads (one,
+        reused: stream order keeps a fold ahead of the launch that overwrites its input)."""
+        nb = self.lib.di_head_conv_stats_bytes(C, H, W)
+        if self._stats is None or self._stats.numel() * 8 < nb or self._stats.device != device:
+            self._stats = torch.empty((nb + 7) // 8, dtype=torch.float64, device=device)
+        return self._stats
+
+    def conv(self, x, weight, bias=None, in_scale=None, in_shift=None, in_elu=False, dilation=1, stats=False):
+        """conv2d(T(x), weight, bias, padding=dilation, dilation=dilation) with
+        T(x) = ELU?(x * in_scale + in_shift) per channel, zero padding after T. weight: the module's
+        [Cout, Cin, k, k] bf16 tensor; bias, in_scale, in_shift: fp32 per-channel vectors or None.
+        Returns y, or (y, stats buffer) with stats=True."""
+        self._check(x)
+        if weight.dtype != torch.bfloat16 or not weight.is_contiguous() or weight.dim() != 4:
+            raise ValueError("head conv weights are the module's contiguous bf16 [Cout, Cin, k, k] tensor")
+        for v in (bias, in_scale, in_shift):
+            if v is not None and (v.dtype != torch.float32 or not v.is_contiguous()):
+                raise ValueError("per-channel vectors are contiguous fp32")
+        _, C, H, W = x.shape
+        cout, cin, k, _ = weight.shape
+        if cin != C:
+            raise ValueError(f"weight takes {cin} channels, the image has {C}")
+        y = torch.empty(1, cout, H, W, dtype=x.dtype, device=x.device)
+        st = self.stats_buffer(cout, H, W, x.device) if stats else None
+        args = self._lib.DiHeadConvArgs(x.data_ptr(), weight.data_ptr(), self._ptr(in_scale).value,
+                                        self._ptr(in_shift).value, self._ptr(bias).value, y.data_ptr(),
+                                        self._ptr(st).value, C, cout, H, W, k, int(dilation), int(bool(in_elu)))
+        self._lib.check(self.lib.di_head_conv(self._lib.DI_BF16, ctypes.byref(args), self._stream()), "di_head_conv")
+        return (y, st) if stats else y
+
+    def plane_stats(self, x):
+        """The statistics buffer of a stored image (one read pass)."""
+        self._check(x)
+        _, C, H, W = x.shape
+        st = self.stats_buffer(C, H, W, x.device)
+        self._lib.check(self.lib.di_plane_stats(self._lib.DI_BF16, self._ptr(x), C, H * W, self._ptr(st),
+                                                self._stream()), "di_plane_stats")
+        return st
+
+    def fold(self, st, C, hw, gamma=None, beta=None, eps=0.0, bias=None, want=("scale", "shift")):
+        """Fold a statistics buffer into fp32 [C] vectors: scale = gamma / sqrt(var + eps),
+        shift = beta - mean * scale, mean = mean (+ bias). Returns the ones named in ``want``, in order."""
+        out = {k: torch.empty(C, dtype=torch.float32, device=st.device) for k in want}
+        self._lib.check(self.lib.di_head_norm_fold(self._ptr(st), C, hw, self._ptr(gamma), self._ptr(beta),
+                                                   ctypes.c_float(eps), self._ptr(bias), self._ptr(out.get("scale")),
+                                                   self._ptr(out.get("shift")), self._ptr(out.get("mean")),
+                                                   self._stream()), "di_head_norm_fold")
+        return tuple(out[k] for k in want)
+
+
 class SEBlock(nn.Module):
     def __init__(self, ch, ratio=16):
         super().__init__()
@@ -127,6 +206,7 @@ class ResNet(nn.Module):
         self.module_name, self.inorm = module_name, inorm
         self.initial_projection = initial_projection
         self.ops = None  # HeadNormOps: fused norm/ELU and SE/residual passes on HIP
+        self.cops = None  # HeadConvOps: the convolutions on HIP, norm + ELU fused into their loads
         C = num_channels
         self.blocks = []
         if initial_projection:
@@ -148,6 +228,10 @@ class ResNet(nn.Module):
 
     def forward(self, x):
         m = self._modules
+        if self.cops is not None:
+            if self.ops is None:
+                raise RuntimeError("the HIP convolutions need the HIP norm passes (use_hip_norm_ops) too")
+            return self._forward_hipconv(x, self.ops, self.cops)
         if self.initial_projection:
             x = m[f"resnet_{self.module_name}_init_proj"](x)
         ops = self.ops
@@ -185,6 +269,42 @@ class ResNet(nn.Module):
         return x
 
 
+    def _forward_hipconv(self, x, ops, cops, in_elu=False):
+        """The blocks with their convolutions on HIP too (HeadConvOps). An InstanceNorm + ELU in
+        front of a convolution never makes a pass of its own: the statistics of the convolution's
+        input -- left by the convolution that produced it, or one read pass over the residual
+        stream for inorm_1 -- are folded to a per-channel scale / shift that the convolution applies
+        as it loads. Biases as in _forward_hip. in_elu: the caller's F.elu in front of this ResNet,
+        applied by init_proj's load."""
+        m = self._modules
+        if self.initial_projection:
+            proj = m[f"resnet_{self.module_name}_init_proj"]
+            x = cops.conv(x, proj.weight, bias=ops.f32(proj.bias), in_elu=in_elu)
+        elif in_elu:
+            x = F.elu(x)
+        _, C, H, W = x.shape
+        hw = H * W
+        for r in self.blocks:
+            res = x
+            st = cops.plane_stats(x) if self.inorm else None
+            for i in (1, 2, 3):
+                conv = m[f"{r}_conv2d_{i}"]
+                if self.inorm:
+                    norm = m[f"{r}_inorm_{i}"]
+                    sc, sh = cops.fold(st, x.shape[1], hw, ops.f32(norm.weight), ops.f32(norm.bias), norm.eps)
+                    x, st = cops.conv(x, conv.weight, in_scale=sc, in_shift=sh, in_elu=True,
+                                      dilation=conv.dilation[0], stats=True)
+                elif i < 3:
+                    x = cops.conv(x, conv.weight, bias=ops.f32(conv.bias), in_elu=True, dilation=conv.dilation[0])
+                else:
+                    x, st = cops.conv(x, conv.weight, in_elu=True, stats=True)
+            conv3, se = m[f"{r}_conv2d_3"], m[f"{r}_se_block"]
+            (mean,) = cops.fold(st, C, hw, bias=ops.f32(conv3.bias), want=("mean",))
+            gate = se.gate_from_mean(mean[None])
+            x = ops.se_scale_add(x, gate, res, out=x, bias=conv3.bias)
+        return x
+
+
 class ResNet2DInputWithOptAttention(nn.Module):
     def __init__(self, num_chunks=14, init_channels=256, num_channels=128, num_classes=2):
         super().__init__()
@@ -195,10 +315,18 @@ class ResNet2DInputWithOptAttention(nn.Module):
                                     extra_blocks=True)
         self.phase2_conv = nn.Conv2d(num_channels, num_classes, 1)
         self.ops = None
+        self.cops = None
 
     def use_hip_norm_ops(self, ops):
         """Route the InstanceNorm+ELU and SE+residual passes through HeadNormOps (or None: torch)."""
         self.ops = self.base_resnet.ops = self.phase2_resnet.ops = ops
+        return self
+
+    def use_hip_convs(self, cops):
+        """Route the ResNets' convolutions through HeadConvOps (or None: torch / MIOpen). bf16 NCHW
+        only, and with the HIP norm passes (use_hip_norm_ops) in place. conv2d_1 and phase2_conv stay
+        on torch."""
+        self.cops = self.base_resnet.cops = self.phase2_resnet.cops = cops
         return self
 
     def forward(self, t):
@@ -210,6 +338,12 @@ class ResNet2DInputWithOptAttention(nn.Module):
     def body(self, x):
         """Everything after the prologue ELU(inorm_1(conv2d_1(t))) (which HeadPrologueOp fuses
         with the pair tensor on HIP)."""
+        if getattr(self, "cops", None) is not None:
+            if self.ops is None:
+                raise RuntimeError("the HIP convolutions need the HIP norm passes (use_hip_norm_ops) too")
+            x = self.base_resnet._forward_hipconv(x, self.ops, self.cops)
+            x = self.phase2_resnet._forward_hipconv(x, self.ops, self.cops, in_elu=True)
+            return self.phase2_conv(F.elu(x))
         x = F.elu(self.base_resnet(x))
         x = F.elu(self.phase2_resnet(x))
         return self.phase2_conv(x)

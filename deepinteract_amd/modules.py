@@ -24,7 +24,7 @@ import torch.nn as nn
 from .config import GeoTConfig, NODE_COUNT_LIMIT, RESIDUE_COUNT_LIMIT
 from .engine import GeoTEngine, HeadPrologueOp, PairTensorOp, gpu_device
 from .graph import GraphBatch, ResidueGraph, batch as batch_graphs, unbatch
-from .head import HeadNormOps, ResNet2DInputWithOptAttention, contact_probs
+from .head import HeadConvOps, HeadNormOps, ResNet2DInputWithOptAttention, contact_probs
 from .ranking import (ContactAucOp, ContactRankOp, confusion_metrics, labels_from_examples,
                       labels_from_examples_batch, topk_metrics)
 
@@ -86,7 +86,8 @@ class LitGINI(nn.Module):
                  num_gnn_attention_heads=4, knn=20, num_interact_layers=14, num_interact_hidden_channels=128,
                  num_classes=2, max_num_graph_nodes=NODE_COUNT_LIMIT, max_num_residues=RESIDUE_COUNT_LIMIT,
                  dtype="f32", head_dtype=torch.float32, precise_head=False, fuse_head_prologue=False,
-                 head_channels_last=False, head_hip_ops=True, pos_prob_threshold=0.5, **kwargs):
+                 head_channels_last=False, head_hip_ops=True, head_convs="torch", pos_prob_threshold=0.5,
+                 **kwargs):
         super().__init__()
         if num_gnn_hidden_channels != 128 or num_gnn_attention_heads != 4:
             # Q/K/V are Linear(H, H) whatever the head count, so a checkpoint trained with another
@@ -118,6 +119,14 @@ class LitGINI(nn.Module):
         # head_hip_ops: the head's InstanceNorm+ELU and SE-gate+residual passes on HIP
         # (head.HeadNormOps; NCHW only, so not with head_channels_last)
         self.head_hip_ops = head_hip_ops and not head_channels_last
+        # head_convs: "torch" (MIOpen) or "hip": the ResNets' 1x1 / dilated 3x3 convolutions on the
+        # matrix cores with the norm + ELU fused into their loads (head.HeadConvOps). bf16 NCHW only.
+        if head_convs not in ("torch", "hip"):
+            raise ValueError(f'head_convs must be "torch" or "hip", got {head_convs!r}')
+        if head_convs == "hip" and (head_dtype != torch.bfloat16 or not head_hip_ops or head_channels_last):
+            raise ValueError('head_convs="hip" needs head_dtype=torch.bfloat16, head_hip_ops=True and no '
+                             "head_channels_last")
+        self.head_convs = head_convs
         self.max_num_residues = max_num_residues
         # pos_prob_threshold: a contact is predicted where its probability reaches it (test_step's
         # rounded predictions and confusion counts; the reference's default)
@@ -161,6 +170,7 @@ class LitGINI(nn.Module):
             pair = PairTensorOp(dev)
             pro = HeadPrologueOp(*self._prologue_w, self._prologue_eps, dev) if self.fuse_head_prologue else None
             self.interact_module.use_hip_norm_ops(HeadNormOps(dev) if self.head_hip_ops else None)
+            self.interact_module.use_hip_convs(HeadConvOps(dev) if self.head_convs == "hip" else None)
             self._dev_ops = (dev, eng, pair, pro)
         return self._dev_ops[1:]
 
@@ -188,7 +198,7 @@ class LitGINI(nn.Module):
             raise RuntimeError(f"{checkpoint_path}: state dict does not match LitGINI ({len(problems)} problems): "
                                + "; ".join(problems[:8]))
         opts = {k: kwargs[k] for k in ("dtype", "head_dtype", "precise_head", "fuse_head_prologue",
-                                       "head_channels_last", "head_hip_ops") if k in kwargs}
+                                       "head_channels_last", "head_hip_ops", "head_convs") if k in kwargs}
         model = cls(num_node_input_feats=cfg.num_node_input_feats, num_gnn_layers=cfg.num_gnn_layers,
                     num_gnn_hidden_channels=cfg.num_gnn_hidden_channels,
                     num_gnn_attention_heads=cfg.num_gnn_attention_heads, knn=cfg.knn,

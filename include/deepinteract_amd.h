@@ -351,6 +351,43 @@ int di_se_scale_add(di_dtype dt, const void* x, const float* scale, const float*
 int di_channel_mean(di_dtype dt, const void* x, int32_t channels, int64_t hw, const float* bias, void* work,
                     float* mean, void* stream);
 
+/* ---- contact-head convolutions with fused norm + ELU (an addition to ABI 8) -----------------
+ * di_head_conv: one 1x1 or dilated 3x3 convolution (stride 1, padding = dilation) of one NCHW image,
+ * bf16 storage, fp32 accumulation on the matrix cores:
+ *   a = in_elu ? ELU(x * in_scale[ci] + in_shift[ci]) : x * in_scale[ci] + in_shift[ci]
+ *       in fp32, rounded to bf16 (RNE); NULL in_scale / in_shift mean 1 / 0. The zero padding applies
+ *       AFTER the transform: a tap outside the image contributes 0.
+ *   y = conv(a, weight) (+ bias[co], nullable), rounded to bf16 (RNE) once.
+ * x [cin, h, w], y [cout, h, w]: bf16, any 2-byte alignment, planes at 64-bit offsets (h * w may be odd
+ * and cin * h * w may pass 2^31); y must not alias x. weight: [cout, cin, ksize, ksize] contiguous bf16
+ * (the module's own tensor). in_scale, in_shift [cin], bias [cout]: fp32. cin 64 / 128 / 256, cout
+ * 64 / 128, ksize 1 or 3, dilation 1 .. 8 (ignored by ksize 1), h, w >= 1.
+ * stats (nullable; 8-B aligned, di_head_conv_stats_bytes(cout, h, w) bytes): per output channel the
+ * (sum y, sum y^2) of the values as stored, one fp64 partial pair per block and channel, no atomics
+ * (bit-reproducible). Layout: int64 n (partials per channel), int64 0, then double [channels][n][2].
+ * di_head_conv_check: the same validation on the host, without a launch. DI_EINVAL: dt other than
+ * DI_BF16, an unsupported cin / cout / ksize / dilation, h or w < 1, NULL x / weight / y, y == x, a
+ * misaligned pointer. DI_ERANGE: more than 2^31 - 1 tiles of 256 pixels (ksize 1), h > 16 * 65535
+ * (ksize 3).
+ * di_plane_stats: the same partials from a stored [channels, hw] image (fp32 or bf16, 16-B aligned) in
+ * one read pass; stats as above (di_head_conv_stats_bytes bytes suffice).
+ * di_head_norm_fold: adds a statistics buffer's partials in a fixed order and writes, per channel,
+ *   scale = gamma / sqrt(var + eps), shift = beta - mean * scale   (InstanceNorm2d as an affine map:
+ *           biased variance, fp64 inside; NULL gamma / beta mean 1 / 0)
+ *   mean  = mean (+ bias[c], nullable)                             (the SE squeeze, as di_channel_mean)
+ * as fp32 [channels]; any of the three outputs may be NULL. hw = h * w of the image. */
+typedef struct {
+  const void* x; const void* weight; const float* in_scale; const float* in_shift; const float* bias;
+  void* y; void* stats;
+  int32_t cin, cout, h, w, ksize, dilation, in_elu;
+} di_head_conv_args;
+int di_head_conv(di_dtype dt, const di_head_conv_args* args, void* stream);
+int di_head_conv_check(di_dtype dt, const di_head_conv_args* args);
+int64_t di_head_conv_stats_bytes(int32_t cout, int32_t h, int32_t w);
+int di_plane_stats(di_dtype dt, const void* x, int32_t channels, int64_t hw, void* stats, void* stream);
+int di_head_norm_fold(const void* stats, int32_t channels, int64_t hw, const float* gamma, const float* beta,
+                      float eps, const float* bias, float* scale, float* shift, float* mean, void* stream);
+
 /* ---- contact ranking (an addition to ABI 8) ------------------------------------------------
  * What LitGINI.test_step does with one complex's logits (deepinteract_modules.py:2018-2101; top-k
  * precision / recall deepinteract_utils.py:977-995), without sorting the map. logits: [1, 2, l1, l2]

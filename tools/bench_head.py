@@ -1,7 +1,8 @@
 """Contact-head benchmark (outside the metric): the dilated-ResNet head
 (deepinteract_modules.py:1155-1248, 14 chunks x {1,2,4,8} + phase 2) on PyTorch-ROCm / MIOpen for one
 C3 complex (input [1,256,L,L]), in five forms: fp32 / bf16 NCHW with torch's InstanceNorm / ELU / SE passes,
-the same with those passes on HIP (head.HeadNormOps, csrc/head_ops.hip), and bf16 channels-last (NHWC). Prints one JSON line: ms per complex, TFLOP/s against the head's
+the same with those passes on HIP (head.HeadNormOps, csrc/head_ops.hip), bf16 channels-last (NHWC), and
+bf16 NCHW with the ResNets' convolutions on HIP too (head.HeadConvOps, csrc/head_conv.hip: bf16_nchw_hipconv). Prints one JSON line: ms per complex, TFLOP/s against the head's
 algorithmic FLOPs (~3.49 M MAC per pixel) and the bf16 logits' max error relative
 to the fp32 logits of the same input.
 
@@ -17,7 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from deepinteract_amd.head import HeadNormOps, ResNet2DInputWithOptAttention  # noqa: E402
+from deepinteract_amd.head import HeadConvOps, HeadNormOps, ResNet2DInputWithOptAttention  # noqa: E402
 from deepinteract_amd.weights import seeded_state_dict  # noqa: E402
 
 
@@ -57,7 +58,7 @@ def main():
     ref = None
     variants = (("f32_nchw", torch.float32, False, False), ("f32_nchw_hipnorm", torch.float32, False, True),
                 ("bf16_nchw", torch.bfloat16, False, False), ("bf16_nchw_hipnorm", torch.bfloat16, False, True),
-                ("bf16_nhwc", torch.bfloat16, True, False))
+                ("bf16_nhwc", torch.bfloat16, True, False), ("bf16_nchw_hipconv", torch.bfloat16, False, True))
     for name, dt, cl, hip in variants:
         if a.only and name not in a.only.split(","):
             continue
@@ -66,6 +67,8 @@ def main():
         m.to(dtype=dt)
         if hip:
             m.use_hip_norm_ops(HeadNormOps(dev))
+        if name.endswith("_hipconv"):
+            m.use_hip_convs(HeadConvOps(dev))
         x = t.to(dt)
         if cl:
             m.to(memory_format=torch.channels_last)
