@@ -86,6 +86,11 @@ class DiHeadConvArgs(ctypes.Structure):
                 ("dilation", ctypes.c_int32), ("in_elu", ctypes.c_int32)]
 
 
+class DiHeadItem(ctypes.Structure):
+    _fields_ = [("px_off", ctypes.c_int64), ("stats_off", ctypes.c_int64), ("h", ctypes.c_int32),
+                ("w", ctypes.c_int32)]
+
+
 # pair-queue words (include/deepinteract_amd.h, di_pair_queue_bytes)
 PQ_READY, PQ_ERROR, PQ_GAVE_UP, PQ_SBYTES, PQ_HBYTES = 0, 32, 33, 40, 42
 
@@ -135,6 +140,12 @@ _SIGS = {
     "di_head_conv_stats_bytes": ([_I, _I, _I], ctypes.c_int64),
     "di_plane_stats": ([_I, _P, _I, ctypes.c_int64, _P, _P], ctypes.c_int),
     "di_head_norm_fold": ([_P, _I, ctypes.c_int64, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P], ctypes.c_int),
+    "di_head_batch_layout": ([_P, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
+    "di_head_conv_batch": ([_I, ctypes.POINTER(DiHeadConvArgs), _P, _P, _I, _P], ctypes.c_int),
+    "di_plane_stats_batch": ([_I, _P, _I, _P, _P, _I, _P, _P], ctypes.c_int),
+    "di_head_norm_fold_batch": ([_P, _I, _P, _P, _I, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P], ctypes.c_int),
+    "di_se_scale_add_batch": ([_I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P], ctypes.c_int),
+    "di_se_gate": ([_P, _P, _P, _P, _P, _I, _I, _I, _P, _P], ctypes.c_int),
     "di_contact_rank_work_bytes": ([ctypes.c_int64, _I], ctypes.c_int64),
     "di_contact_rank": ([_I, _P, _I, _I, _I, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
     "di_contact_auc_work_bytes": ([ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),

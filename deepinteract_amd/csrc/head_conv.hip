@@ -26,6 +26,8 @@
 //        product over the halo shifted by (ty d, tx d): a dilated 3x3 is nine shifted 1x1 products.
 //        Three instantiations by LDS size (d <= 2, <= 4, <= 8: 63 / 74 / 102 KiB for Cout = 64).
 // Plane offsets (channel * hw) are 64-bit. Ordinary launches; no block waits for another.
+// di_head_conv_batch runs the same block code over a packed ragged batch of images in one launch
+// (k_head_conv_batch below; the layout and the item table: include/deepinteract_amd.h).
 //
 // Statistics (optional): per output channel (sum y, sum y^2) of the values AS STORED (after the bf16
 // rounding). A thread sums its 4 pixels in fp32 (as k_inorm_stats sums a vector's elements); from
@@ -37,6 +39,7 @@
 #include <stdint.h>
 #include "common.h"
 #include "../../include/deepinteract_amd.h"
+#include "head_batch.h"
 
 namespace di {
 
@@ -98,8 +101,12 @@ constexpr int hc_blocks_per_cu(int ks, int cout, int dmax) {
   return ks == 1 || (cout == 64 && dmax <= 4) ? 2 : 1;
 }
 
+// One block's work, for block (bx, by) of an image's own gx x gy grid (1x1: gy = 1). The single call's
+// kernel and the batch's both run exactly this, so an image's output and statistics partials do not
+// depend on which of the two launched it.
 template <int KS, int COUT, int DMAX>
-__global__ __launch_bounds__(HC_THREADS, hc_blocks_per_cu(KS, COUT, DMAX)) void k_head_conv(const HcArgs a) {
+__device__ __forceinline__ void head_conv_body(const HcArgs& a, const int bx, const int by, const int gx,
+                                               const int gy) {
   constexpr int TAPS = KS * KS;
   constexpr int NCB = COUT / 16;
   constexpr int HALO = HC_TILE + 2 * DMAX;
@@ -119,8 +126,8 @@ __global__ __launch_bounds__(HC_THREADS, hc_blocks_per_cu(KS, COUT, DMAX)) void 
   const int d = KS == 3 ? a.dil : 0;
   const int halo = HC_TILE + 2 * d;               // <= HALO: the host picks DMAX >= d
   const int npx = KS == 3 ? halo * halo : HC_PIX;
-  const int y0 = blockIdx.y * HC_TILE, x0 = blockIdx.x * HC_TILE;  // 3x3
-  const int64_t base = (int64_t)blockIdx.x * HC_PIX;               // 1x1
+  const int y0 = by * HC_TILE, x0 = bx * HC_TILE;  // 3x3
+  const int64_t base = (int64_t)bx * HC_PIX;  // 1x1
   const int64_t hw = a.hw;
 
   for (int c = tid; c < a.cin; c += HC_THREADS) {
@@ -265,8 +272,8 @@ __global__ __launch_bounds__(HC_THREADS, hc_blocks_per_cu(KS, COUT, DMAX)) void 
     }
   if (stats) {
     __syncthreads();
-    const int64_t nblk = (int64_t)gridDim.x * gridDim.y;
-    const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t nblk = (int64_t)gx * gy;
+    const int64_t blk = (int64_t)by * gx + bx;
     double* part = a.stats + 2;
     if (tid < COUT) {
       double s = 0.0, ss = 0.0;
@@ -282,6 +289,45 @@ __global__ __launch_bounds__(HC_THREADS, hc_blocks_per_cu(KS, COUT, DMAX)) void 
       reinterpret_cast<int64_t*>(a.stats)[1] = 0;
     }
   }
+}
+
+template <int KS, int COUT, int DMAX>
+__global__ __launch_bounds__(HC_THREADS, hc_blocks_per_cu(KS, COUT, DMAX)) void k_head_conv(const HcArgs a) {
+  head_conv_body<KS, COUT, DMAX>(a, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
+}
+
+// The batch: blockIdx.z names the item, the x / y grid is the largest item's, and a block past its own
+// item's tile count leaves at once -- as a whole, before any barrier. (The project's idiom, as the
+// rank / AUC batches: against a prefix table of tiles it needs no second table and no search per
+// block, and a block that only reads its item and leaves costs far less than the launch it saves; a
+// batch of one large and many small images starts at most (count - 1) x the large one's tiles of them.)
+// a.x, a.y, a.stats, a.in_scale, a.in_shift are the packed buffers' bases; h, wd, hw are unused.
+template <int KS, int COUT, int DMAX>
+__global__ __launch_bounds__(HC_THREADS, hc_blocks_per_cu(KS, COUT, DMAX)) void k_head_conv_batch(
+    const HcArgs a, const di_head_item* __restrict__ items) {
+  const int z = blockIdx.z;
+  const int h = items[z].h, wd = items[z].w;
+  const int64_t hw = (int64_t)h * wd;
+  int gx, gy;
+  if constexpr (KS == 3) {
+    gx = (wd + HC_TILE - 1) / HC_TILE;
+    gy = (h + HC_TILE - 1) / HC_TILE;
+  } else {
+    gx = (int)((hw + HC_PIX - 1) / HC_PIX);
+    gy = 1;
+  }
+  if ((int)blockIdx.x >= gx || (int)blockIdx.y >= gy) return;
+  const int64_t px = items[z].px_off;
+  HcArgs b = a;
+  b.x = a.x + (int64_t)a.cin * px;
+  b.y = a.y + (int64_t)COUT * px;
+  b.stats = a.stats ? reinterpret_cast<double*>(reinterpret_cast<char*>(a.stats) + items[z].stats_off) : nullptr;
+  b.in_scale = a.in_scale ? a.in_scale + (int64_t)z * a.cin : nullptr;
+  b.in_shift = a.in_shift ? a.in_shift + (int64_t)z * a.cin : nullptr;
+  b.hw = hw;
+  b.h = h;
+  b.wd = wd;
+  head_conv_body<KS, COUT, DMAX>(b, blockIdx.x, blockIdx.y, gx, gy);
 }
 
 // blocks of a launch = partials per channel
@@ -306,8 +352,28 @@ static int hc_check(di_dtype dt, const di_head_conv_args* a) {
 }
 
 template <int KS, int COUT, int DMAX>
-static void hc_launch(const HcArgs& k, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_head_conv<KS, COUT, DMAX>), grid, dim3(HC_THREADS), 0, s, k);
+static void hc_launch(const HcArgs& k, dim3 grid, hipStream_t s, const di_head_item* items = nullptr) {
+  if (items) hipLaunchKernelGGL((k_head_conv_batch<KS, COUT, DMAX>), grid, dim3(HC_THREADS), 0, s, k, items);
+  else hipLaunchKernelGGL((k_head_conv<KS, COUT, DMAX>), grid, dim3(HC_THREADS), 0, s, k);
+}
+
+// the instantiation for (ksize, cout, dilation); items: the batch's device table, or NULL
+static void hc_dispatch(const HcArgs& k, int ksize, int cout, int d, dim3 grid, hipStream_t s,
+                        const di_head_item* items = nullptr) {
+  const bool wide = cout == 128;
+  if (ksize == 1) {
+    if (wide) hc_launch<1, 128, 0>(k, grid, s, items);
+    else hc_launch<1, 64, 0>(k, grid, s, items);
+  } else if (d <= 2) {
+    if (wide) hc_launch<3, 128, 2>(k, grid, s, items);
+    else hc_launch<3, 64, 2>(k, grid, s, items);
+  } else if (d <= 4) {
+    if (wide) hc_launch<3, 128, 4>(k, grid, s, items);
+    else hc_launch<3, 64, 4>(k, grid, s, items);
+  } else {
+    if (wide) hc_launch<3, 128, 8>(k, grid, s, items);
+    else hc_launch<3, 64, 8>(k, grid, s, items);
+  }
 }
 
 }  // namespace di
@@ -344,25 +410,66 @@ extern "C" int di_head_conv(di_dtype dt, const di_head_conv_args* args, void* st
   k.dil = args->dilation;
   k.in_elu = args->in_elu ? 1 : 0;
   hipStream_t s = (hipStream_t)stream;
-  const bool wide = args->cout == 128;
-  if (args->ksize == 1) {
-    const dim3 grid((unsigned)hc_blocks(1, args->h, args->w));
-    if (wide) hc_launch<1, 128, 0>(k, grid, s);
-    else hc_launch<1, 64, 0>(k, grid, s);
-  } else {
-    const dim3 grid((args->w + HC_TILE - 1) / HC_TILE, (args->h + HC_TILE - 1) / HC_TILE);
-    const int d = args->dilation;
-    if (d <= 2) {
-      if (wide) hc_launch<3, 128, 2>(k, grid, s);
-      else hc_launch<3, 64, 2>(k, grid, s);
-    } else if (d <= 4) {
-      if (wide) hc_launch<3, 128, 4>(k, grid, s);
-      else hc_launch<3, 64, 4>(k, grid, s);
-    } else {
-      if (wide) hc_launch<3, 128, 8>(k, grid, s);
-      else hc_launch<3, 64, 8>(k, grid, s);
-    }
+  const dim3 grid = args->ksize == 1 ? dim3((unsigned)hc_blocks(1, args->h, args->w))
+                                     : dim3((args->w + HC_TILE - 1) / HC_TILE, (args->h + HC_TILE - 1) / HC_TILE);
+  hc_dispatch(k, args->ksize, args->cout, args->dilation, grid, s);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DI_OK : (int)e;
+}
+
+extern "C" int di_head_batch_layout(di_head_item* items, int32_t count, int64_t* total_px, int64_t* stats_bytes) {
+  if (!items || !total_px || !stats_bytes || count < 1) return DI_EINVAL;
+  if (count > DI_BATCH_MAX) return DI_ERANGE;
+  int64_t px = 0, st = 0;
+  for (int32_t i = 0; i < count; ++i) {
+    if (items[i].h < 1 || items[i].w < 1) return DI_EINVAL;
+    px += (int64_t)items[i].h * items[i].w;
+    if (px > HB_MAX_PX) return DI_ERANGE;
   }
+  px = 0;
+  for (int32_t i = 0; i < count; ++i) {
+    items[i].px_off = px;
+    items[i].stats_off = st;
+    px += (int64_t)items[i].h * items[i].w;
+    st += hb_stats_room(items[i].h, items[i].w);
+  }
+  *total_px = px;
+  *stats_bytes = st;
+  return DI_OK;
+}
+
+extern "C" int di_head_conv_batch(di_dtype dt, const di_head_conv_args* args, const di_head_item* items,
+                                  const di_head_item* items_dev, int32_t count, void* stream) {
+  if (!args) return DI_EINVAL;
+  int rc = hb_check_items(items, items_dev, count);
+  if (rc != DI_OK) return rc;
+  unsigned gx = 1, gy = 1;
+  di_head_conv_args one = *args;
+  for (int32_t i = 0; i < count; ++i) {  // the single call's checks, on every item's own sizes
+    one.h = items[i].h;
+    one.w = items[i].w;
+    rc = hc_check(dt, &one);
+    if (rc != DI_OK) return rc;
+    const unsigned ix = args->ksize == 1 ? (unsigned)hc_blocks(1, one.h, one.w) : (unsigned)((one.w + HC_TILE - 1) / HC_TILE);
+    const unsigned iy = args->ksize == 1 ? 1u : (unsigned)((one.h + HC_TILE - 1) / HC_TILE);
+    gx = ix > gx ? ix : gx;
+    gy = iy > gy ? iy : gy;
+  }
+  HcArgs k;
+  k.x = (const u16*)args->x;
+  k.w = (const u16*)args->weight;
+  k.in_scale = args->in_scale;
+  k.in_shift = args->in_shift;
+  k.bias = args->bias;
+  k.y = (u16*)args->y;
+  k.stats = (double*)args->stats;
+  k.hw = 0;
+  k.cin = args->cin;
+  k.h = 0;
+  k.wd = 0;
+  k.dil = args->dilation;
+  k.in_elu = args->in_elu ? 1 : 0;
+  hc_dispatch(k, args->ksize, args->cout, args->dilation, dim3(gx, gy, (unsigned)count), (hipStream_t)stream, items_dev);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
 }

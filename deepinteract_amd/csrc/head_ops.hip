@@ -18,6 +18,9 @@
 //    alone, into a self-describing buffer, and the fold of such a buffer -- written by this pass or by
 //    a convolution's epilogue -- into the per-channel scale / shift the next convolution applies as it
 //    loads, or into the SE squeeze.
+//  * di_plane_stats_batch / di_head_norm_fold_batch / di_se_scale_add_batch: the same passes over a
+//    packed ragged batch of images, one launch each, every image with the single call's decomposition
+//    and bits; di_se_gate: SEBlock's two linears, ReLU and sigmoid for the batch's means, in fp32.
 // The convs before an InstanceNorm run without their bias (a per-channel constant cancels in
 // the normalisation exactly), so the head does no separate bias-add passes.
 // fp32 accumulation everywhere, fp64 for the statistics; bf16 storage rounds once (RNE).
@@ -26,6 +29,7 @@
 #include <stdint.h>
 #include "common.h"
 #include "../../include/deepinteract_amd.h"
+#include "head_batch.h"
 
 namespace di {
 
@@ -100,17 +104,27 @@ struct Plane {
   __device__ int64_t scalar_at(int64_t i, int) const { return i < nh ? h0 + i : t0 + (i - nh); }
 };
 
+// blocks per channel: fill the chip (>= ~2048 blocks) without slices under 2 vectors per thread
+__host__ __device__ static inline int ho_split(int channels, int64_t hw, int vec) {
+  int split = (2048 + channels - 1) / channels;
+  split = split < 1 ? 1 : (split > HO_MAX_SPLIT ? HO_MAX_SPLIT : split);
+  const int64_t nvec = hw / vec;
+  while (split > 1 && nvec / split < 2 * HO_THREADS) split >>= 1;  // >= 2 vectors per thread
+  return split;
+}
+
+// Slice bx of the `split` slices of channel c's plane. The single kernels and the batch's run these
+// bodies, an image's own split and sizes in hand, so both give an image the same bits.
 template <typename T>
-__global__ __launch_bounds__(HO_THREADS) void k_inorm_stats(const T* __restrict__ x, int64_t hw,
-                                                            double* __restrict__ part,
-                                                            int64_t* __restrict__ hdr = nullptr) {
+__device__ __forceinline__ void inorm_stats_body(const T* __restrict__ x, int64_t hw, double* __restrict__ part,
+                                                 int64_t* __restrict__ hdr, const int c, const int split,
+                                                 const int bx) {
   using V = Vec<T>;
-  const int c = blockIdx.y, split = gridDim.x;
-  if (hdr && c == 0 && blockIdx.x == 0 && threadIdx.x == 0) {  // di_plane_stats: partials per channel
+  if (hdr && c == 0 && bx == 0 && threadIdx.x == 0) {  // di_plane_stats: partials per channel
     hdr[0] = split;
     hdr[1] = 0;
   }
-  const Plane P(hw, V::N, c, split, blockIdx.x);
+  const Plane P(hw, V::N, c, split, bx);
   double s = 0.0, ss = 0.0;
   for (int64_t i = P.lo + threadIdx.x; i < P.hi; i += HO_THREADS) {
     float v[V::N];
@@ -124,7 +138,7 @@ __global__ __launch_bounds__(HO_THREADS) void k_inorm_stats(const T* __restrict_
     s += fs;
     ss += fss;
   }
-  if (blockIdx.x == split - 1) {
+  if (bx == split - 1) {
     const int64_t ns = P.nscalar(V::N);
     for (int64_t i = threadIdx.x; i < ns; i += HO_THREADS) {
       const float v = V::ld1(x + P.scalar_at(i, V::N));
@@ -150,9 +164,16 @@ __global__ __launch_bounds__(HO_THREADS) void k_inorm_stats(const T* __restrict_
       a += red[0][w];
       b += red[1][w];
     }
-    part[((int64_t)c * split + blockIdx.x) * 2 + 0] = a;
-    part[((int64_t)c * split + blockIdx.x) * 2 + 1] = b;
+    part[((int64_t)c * split + bx) * 2 + 0] = a;
+    part[((int64_t)c * split + bx) * 2 + 1] = b;
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(HO_THREADS) void k_inorm_stats(const T* __restrict__ x, int64_t hw,
+                                                            double* __restrict__ part,
+                                                            int64_t* __restrict__ hdr = nullptr) {
+  inorm_stats_body<T>(x, hw, part, hdr, blockIdx.y, gridDim.x, blockIdx.x);
 }
 
 __device__ __forceinline__ float elu1(float z) { return z > 0.f ? z : expm1f(z); }
@@ -207,15 +228,14 @@ __global__ __launch_bounds__(HO_THREADS) void k_inorm_apply(const T* __restrict_
 }
 
 template <typename T>
-__global__ __launch_bounds__(HO_THREADS) void k_se_scale_add(const T* __restrict__ x, const float* __restrict__ s,
-                                                             const float* __restrict__ bias,
-                                                             const T* __restrict__ res, int64_t hw,
-                                                             T* __restrict__ y) {
+__device__ __forceinline__ void se_scale_add_body(const T* __restrict__ x, const float* __restrict__ s,
+                                                  const float* __restrict__ bias, const T* __restrict__ res,
+                                                  int64_t hw, T* __restrict__ y, const int c, const int split,
+                                                  const int bx) {
 #pragma clang fp contract(off)  // + bias, * s and + res round separately, as torch's kernels do
   using V = Vec<T>;
-  const int c = blockIdx.y, split = gridDim.x;
   const float g = s[c], bc = bias ? bias[c] : 0.f;
-  const Plane P(hw, V::N, c, split, blockIdx.x);
+  const Plane P(hw, V::N, c, split, bx);
   for (int64_t i = P.lo + threadIdx.x; i < P.hi; i += HO_THREADS) {
     float a[V::N], r[V::N];
     V::load(x + i * V::N, a);
@@ -225,13 +245,50 @@ __global__ __launch_bounds__(HO_THREADS) void k_se_scale_add(const T* __restrict
     for (int q = 0; q < V::N; ++q) a[q] = V::round(V::round(a[q] + bc) * g) + r[q];
     V::store(y + i * V::N, a);
   }
-  if (blockIdx.x == split - 1) {
+  if (bx == split - 1) {
     const int64_t ns = P.nscalar(V::N);
     for (int64_t i = threadIdx.x; i < ns; i += HO_THREADS) {
       const int64_t e = P.scalar_at(i, V::N);
       V::st1(y + e, V::round(V::round(V::ld1(x + e) + bc) * g) + V::ld1(res + e));
     }
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(HO_THREADS) void k_se_scale_add(const T* __restrict__ x, const float* __restrict__ s,
+                                                             const float* __restrict__ bias,
+                                                             const T* __restrict__ res, int64_t hw,
+                                                             T* __restrict__ y) {
+  se_scale_add_body<T>(x, s, bias, res, hw, y, blockIdx.y, gridDim.x, blockIdx.x);
+}
+
+// The batch (blockIdx.z = item; see k_head_conv_batch): an item's planes start at channels * px_off
+// elements, 128-B aligned, so Plane splits them as the single call does with the item as its buffer;
+// the slice count is the single call's for that item's hw, and blocks past it leave before any barrier.
+__global__ __launch_bounds__(HO_THREADS) void k_plane_stats_batch(const u16* __restrict__ x, int channels,
+                                                                  const di_head_item* __restrict__ items,
+                                                                  char* __restrict__ stats) {
+  const di_head_item it = items[blockIdx.z];
+  const int64_t hw = (int64_t)it.h * it.w;
+  const int split = ho_split(channels, hw, 8);
+  if ((int)blockIdx.x >= split) return;
+  int64_t* hdr = reinterpret_cast<int64_t*>(stats + it.stats_off);
+  inorm_stats_body<u16>(x + (int64_t)channels * it.px_off, hw, reinterpret_cast<double*>(hdr) + 2, hdr, blockIdx.y,
+                        split, blockIdx.x);
+}
+
+__global__ __launch_bounds__(HO_THREADS) void k_se_scale_add_batch(const u16* __restrict__ x,
+                                                                   const float* __restrict__ s,
+                                                                   const float* __restrict__ bias,
+                                                                   const u16* __restrict__ res, int channels,
+                                                                   const di_head_item* __restrict__ items,
+                                                                   u16* __restrict__ y) {
+  const di_head_item it = items[blockIdx.z];
+  const int64_t hw = (int64_t)it.h * it.w, off = (int64_t)channels * it.px_off;
+  const int split = ho_split(channels, hw, 8);
+  if ((int)blockIdx.x >= split) return;
+  se_scale_add_body<u16>(x + off, s + (int64_t)blockIdx.z * channels, bias, res + off, hw, y + off, blockIdx.y, split,
+                         blockIdx.x);
 }
 
 // mean[c] = sum of the channel's partials / hw (+ bias[c]): SEBlock's x.mean(dim=(2, 3)) of a
@@ -248,13 +305,11 @@ __global__ void k_channel_mean(const double* __restrict__ part, int split, int c
 // One block per channel adds the channel's n partials (n from the buffer's header) in a fixed order
 // -- thread t takes partials t, t + 256, ..., then a tree over the threads -- and derives, in fp64,
 // mean, biased variance, scale = gamma / sqrt(var + eps), shift = beta - mean * scale.
-__global__ __launch_bounds__(HO_THREADS) void k_head_norm_fold(const double* __restrict__ stats, int64_t hw,
-                                                               const float* __restrict__ gamma,
-                                                               const float* __restrict__ beta, float eps,
-                                                               const float* __restrict__ bias,
-                                                               float* __restrict__ scale, float* __restrict__ shift,
-                                                               float* __restrict__ mean) {
-  const int c = blockIdx.x;
+__device__ __forceinline__ void head_norm_fold_body(const double* __restrict__ stats, int64_t hw,
+                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                    float eps, const float* __restrict__ bias,
+                                                    float* __restrict__ scale, float* __restrict__ shift,
+                                                    float* __restrict__ mean, const int c) {
   const int64_t n = reinterpret_cast<const int64_t*>(stats)[0];
   const double* part = stats + 2 + (int64_t)c * n * 2;
   double a = 0.0, b = 0.0;
@@ -283,14 +338,55 @@ __global__ __launch_bounds__(HO_THREADS) void k_head_norm_fold(const double* __r
     if (mean) mean[c] = (float)(m + (bias ? (double)bias[c] : 0.0));
   }
 }
+__global__ __launch_bounds__(HO_THREADS) void k_head_norm_fold(const double* __restrict__ stats, int64_t hw,
+                                                               const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, float eps,
+                                                               const float* __restrict__ bias,
+                                                               float* __restrict__ scale, float* __restrict__ shift,
+                                                               float* __restrict__ mean) {
+  head_norm_fold_body(stats, hw, gamma, beta, eps, bias, scale, shift, mean, blockIdx.x);
+}
+// grid (channels, count): item blockIdx.y's buffer into row blockIdx.y of scale / shift / mean
+__global__ __launch_bounds__(HO_THREADS) void k_head_norm_fold_batch(const char* __restrict__ stats, int channels,
+                                                                     const di_head_item* __restrict__ items,
+                                                                     const float* __restrict__ gamma,
+                                                                     const float* __restrict__ beta, float eps,
+                                                                     const float* __restrict__ bias,
+                                                                     float* __restrict__ scale,
+                                                                     float* __restrict__ shift,
+                                                                     float* __restrict__ mean) {
+  const di_head_item it = items[blockIdx.y];
+  const int64_t row = (int64_t)blockIdx.y * channels;
+  head_norm_fold_body(reinterpret_cast<const double*>(stats + it.stats_off), (int64_t)it.h * it.w, gamma, beta, eps,
+                      bias, scale ? scale + row : nullptr, shift ? shift + row : nullptr, mean ? mean + row : nullptr,
+                      blockIdx.x);
+}
 
-// blocks per channel: fill the chip (>= ~2048 blocks) without slices under 2 vectors per thread
-static int ho_split(int channels, int64_t hw, int vec) {
-  int split = (2048 + channels - 1) / channels;
-  split = split < 1 ? 1 : (split > HO_MAX_SPLIT ? HO_MAX_SPLIT : split);
-  const int64_t nvec = hw / vec;
-  while (split > 1 && nvec / split < 2 * HO_THREADS) split >>= 1;  // >= 2 vectors per thread
-  return split;
+// SEBlock's gate for `count` rows of means, one block per row: the hidden units by one thread each
+// (`channels` fused multiply-adds in index order from the bias), then one thread per channel. fp32.
+constexpr int SG_MAX_C = 1024, SG_MAX_H = 64;
+__global__ void k_se_gate(const float* __restrict__ mean, const float* __restrict__ w1,
+                          const float* __restrict__ b1, const float* __restrict__ w2,
+                          const float* __restrict__ b2, int channels, int hidden, float* __restrict__ gate) {
+  __shared__ float m[SG_MAX_C];
+  __shared__ float hid[SG_MAX_H];
+  const int64_t row = (int64_t)blockIdx.x * channels;
+  for (int c = threadIdx.x; c < channels; c += blockDim.x) m[c] = mean[row + c];
+  __syncthreads();
+  if ((int)threadIdx.x < hidden) {
+    const float* w = w1 + (int64_t)threadIdx.x * channels;
+    float acc = b1[threadIdx.x];
+    for (int c = 0; c < channels; ++c) acc = fmaf(w[c], m[c], acc);
+    hid[threadIdx.x] = acc > 0.f ? acc : 0.f;
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < channels; c += blockDim.x) {
+    const float* w = w2 + (int64_t)c * hidden;
+    float acc = b2[c];
+    for (int j = 0; j < hidden; ++j) acc = fmaf(w[j], hid[j], acc);
+    acc = acc > 0.f ? acc : 0.f;
+    gate[row + c] = 1.f / (1.f + __expf(-acc));
+  }
 }
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -382,6 +478,68 @@ extern "C" int di_head_norm_fold(const void* stats, int32_t channels, int64_t hw
   if (!(eps >= 0.f)) return DI_EINVAL;
   hipLaunchKernelGGL(k_head_norm_fold, dim3(channels), dim3(HO_THREADS), 0, (hipStream_t)stream,
                      (const double*)stats, hw, gamma, beta, eps, bias, scale, shift, mean);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DI_OK : (int)e;
+}
+
+// the widest split any item of the batch takes (the grid's x size)
+static int ho_max_split(const di_head_item* items, int32_t count, int channels) {
+  int m = 1;
+  for (int32_t i = 0; i < count; ++i) {
+    const int sp = ho_split(channels, (int64_t)items[i].h * items[i].w, 8);
+    m = sp > m ? sp : m;
+  }
+  return m;
+}
+
+extern "C" int di_plane_stats_batch(di_dtype dt, const void* x, int32_t channels, const di_head_item* items,
+                                    const di_head_item* items_dev, int32_t count, void* stats, void* stream) {
+  if (!x || !stats || channels <= 0 || channels > 128 || dt != DI_BF16) return DI_EINVAL;
+  if (!aligned16(x) || ((uintptr_t)stats & 7) != 0 || (channels & 7) != 0) return DI_EINVAL;
+  const int rc = hb_check_items(items, items_dev, count);
+  if (rc != DI_OK) return rc;
+  const dim3 grid(ho_max_split(items, count, channels), channels, count);
+  hipLaunchKernelGGL(k_plane_stats_batch, grid, dim3(HO_THREADS), 0, (hipStream_t)stream, (const u16*)x, channels,
+                     items_dev, (char*)stats);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DI_OK : (int)e;
+}
+
+extern "C" int di_head_norm_fold_batch(const void* stats, int32_t channels, const di_head_item* items,
+                                       const di_head_item* items_dev, int32_t count, const float* gamma,
+                                       const float* beta, float eps, const float* bias, float* scale, float* shift,
+                                       float* mean, void* stream) {
+  if (!stats || ((uintptr_t)stats & 7) != 0 || channels <= 0 || channels > 128) return DI_EINVAL;
+  if (!(eps >= 0.f)) return DI_EINVAL;
+  const int rc = hb_check_items(items, items_dev, count);
+  if (rc != DI_OK) return rc;
+  hipLaunchKernelGGL(k_head_norm_fold_batch, dim3(channels, count), dim3(HO_THREADS), 0, (hipStream_t)stream,
+                     (const char*)stats, channels, items_dev, gamma, beta, eps, bias, scale, shift, mean);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DI_OK : (int)e;
+}
+
+extern "C" int di_se_scale_add_batch(di_dtype dt, const void* x, const float* scale, const float* bias,
+                                     const void* res, int32_t channels, const di_head_item* items,
+                                     const di_head_item* items_dev, int32_t count, void* y, void* stream) {
+  if (!x || !scale || !res || !y || channels <= 0 || channels > 65535 || dt != DI_BF16) return DI_EINVAL;
+  if (!aligned16(x) || !aligned16(res) || !aligned16(y) || (channels & 7) != 0) return DI_EINVAL;
+  const int rc = hb_check_items(items, items_dev, count);
+  if (rc != DI_OK) return rc;
+  const dim3 grid(ho_max_split(items, count, channels), channels, count);
+  hipLaunchKernelGGL(k_se_scale_add_batch, grid, dim3(HO_THREADS), 0, (hipStream_t)stream, (const u16*)x, scale, bias,
+                     (const u16*)res, channels, items_dev, (u16*)y);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DI_OK : (int)e;
+}
+
+extern "C" int di_se_gate(const float* mean, const float* w1, const float* b1, const float* w2, const float* b2,
+                          int32_t count, int32_t channels, int32_t hidden, float* gate, void* stream) {
+  if (!mean || !w1 || !b1 || !w2 || !b2 || !gate) return DI_EINVAL;
+  if (count < 1 || channels < 1 || channels > SG_MAX_C || hidden < 1 || hidden > SG_MAX_H) return DI_EINVAL;
+  const int threads = (channels + 63) / 64 * 64 < 256 ? (channels + 63) / 64 * 64 : 256;
+  hipLaunchKernelGGL(k_se_gate, dim3(count), dim3(threads), 0, (hipStream_t)stream, mean, w1, b1, w2, b2, channels,
+                     hidden, gate);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
 }

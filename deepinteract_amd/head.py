@@ -1,5 +1,6 @@
 """Dilated-ResNet contact head — on PyTorch-ROCm (MIOpen convolutions) by default, as north_star
-specifies; opt-in, the bf16 head's convolutions run on HIP (HeadConvOps, csrc/head_conv.hip). Module/parameter names match the reference's ``interact_module`` so reference
+specifies; opt-in, the bf16 head's convolutions run on HIP (HeadConvOps, csrc/head_conv.hip), for one complex at a
+time or for a ragged batch of complexes with one launch per pass (HeadBatch, body_batch). Module/parameter names match the reference's ``interact_module`` so reference
 state dicts load unchanged: ResNet2DInputWithOptAttention (deepinteract_modules.py:1155-1248),
 ResNet (:973-1106), SEBlock (:954-970). The optional regional attention (MHA2D) is not part
 of the default model (``use_interact_attention=False``) and is not implemented.
@@ -103,6 +104,112 @@ class HeadNormOps:
         return y
 
 
+    def se_scale_add_batch(self, hb, x, scale, res, out=None, bias=None):
+        """se_scale_add for every image of a HeadBatch in one launch: x, res, out packed [C * pixels] bf16
+        buffers (out may be x or res; None: a new buffer), scale [count, C] fp32 rows, bias [C] shared."""
+        C = scale.shape[1]
+        hb.check_packed(x, C), hb.check_packed(res, C)
+        if scale.dtype != torch.float32 or not scale.is_contiguous() or scale.shape[0] != hb.count:
+            raise ValueError("the batch's gates are contiguous fp32 [count, C] rows")
+        b = self.f32(bias)
+        y = torch.empty_like(x) if out is None else out
+        self._lib.check(self.lib.di_se_scale_add_batch(self._lib.DI_BF16, ctypes.c_void_p(x.data_ptr()),
+                                                       ctypes.c_void_p(scale.data_ptr()),
+                                                       ctypes.c_void_p(0 if b is None else b.data_ptr()),
+                                                       ctypes.c_void_p(res.data_ptr()), C, hb.items, hb.items_ptr,
+                                                       hb.count, ctypes.c_void_p(y.data_ptr()), self._stream()),
+                        "di_se_scale_add_batch")
+        return y
+
+    def se_gate(self, se, mean, out=None):
+        """SEBlock's gate sigmoid(relu(linear2(relu(linear1(mean))))) for [count, C] fp32 means, all in
+        fp32 with a fixed accumulation order (di_se_gate; one launch): fp32 [count, C]."""
+        if mean.dtype != torch.float32 or mean.dim() != 2 or not mean.is_contiguous() or not mean.is_cuda:
+            raise ValueError("se_gate takes contiguous fp32 [count, C] GPU means")
+        count, C = mean.shape
+        w1, b1, w2, b2 = (self.f32(t) for t in (se.linear1.weight, se.linear1.bias, se.linear2.weight,
+                                                 se.linear2.bias))
+        hidden = w1.shape[0]
+        if tuple(w1.shape) != (hidden, C) or tuple(w2.shape) != (C, hidden):
+            raise ValueError(f"the SE block takes {w1.shape[1]} channels, the means have {C}")
+        g = torch.empty_like(mean) if out is None else out
+        self._lib.check(self.lib.di_se_gate(*(ctypes.c_void_p(t.data_ptr()) for t in (mean, w1, b1, w2, b2)),
+                                            count, C, hidden, ctypes.c_void_p(g.data_ptr()), self._stream()),
+                        "di_se_gate")
+        return g
+
+
+class HeadBatch:
+    """A ragged batch of head images for the batched HIP head (di_head_item, include/deepinteract_amd.h):
+    built once from the images' (h, w), it owns the device copy of the item table, the statistics
+    buffer, the per-item fp32 rows (scale, shift, mean, gate) and the arena every layer of a forward
+    works in -- two 128-channel packed buffers (the residual stream and a block's output, swapping
+    roles from block to block) and two 64-channel ones: 768 B per pixel. Nothing is allocated per layer
+    and nothing is copied to the device after construction.
+
+    Item i of a packed [C * pixels] buffer is the contiguous NCHW image ``view(buf, C, i)``. Fill
+    ``input(i)`` (a [1, 128, h, w] view of the residual stream) with ELU(inorm_1(conv2d_1(T_i))) for
+    every i, then call ``ResNet2DInputWithOptAttention.body_batch(batch)``."""
+
+    CHANNELS = 128
+
+    def __init__(self, shapes, device):
+        from . import _lib
+        from .ranking import _table_to_device
+        shapes = [(int(h), int(w)) for h, w in shapes]
+        self.shapes, self.count = shapes, len(shapes)
+        if not 1 <= self.count <= _lib.DI_BATCH_MAX:
+            raise ValueError(f"a head batch holds 1 .. {_lib.DI_BATCH_MAX} images, got {self.count}")
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.items = (_lib.DiHeadItem * self.count)()
+        for it, (h, w) in zip(self.items, shapes):
+            it.h, it.w = h, w
+        px, nb = ctypes.c_int64(), ctypes.c_int64()
+        rc = _lib.load().di_head_batch_layout(self.items, self.count, ctypes.byref(px), ctypes.byref(nb))
+        if rc != 0:
+            raise ValueError(f"head batch of shapes {shapes}: code {rc}")
+        self.pixels, self.stats_bytes = px.value, nb.value
+        self.px_off = [it.px_off for it in self.items]
+        self.stats_off = [it.stats_off for it in self.items]
+        self.items_dev = _table_to_device(self.items, self.device)
+        self.items_ptr = ctypes.c_void_p(self.items_dev.data_ptr())
+        C = self.CHANNELS
+        bf = dict(dtype=torch.bfloat16, device=self.device)
+        self.wide = [torch.empty(C * self.pixels, **bf) for _ in range(2)]
+        self.half = [torch.empty(C // 2 * self.pixels, **bf) for _ in range(2)]
+        self.stats = torch.empty(self.stats_bytes // 8, dtype=torch.float64, device=self.device)
+        self.rows = torch.empty(4, self.count, C, dtype=torch.float32, device=self.device)
+
+    def check_packed(self, buf, C):
+        if buf.dtype != torch.bfloat16 or not buf.is_contiguous() or buf.numel() != C * self.pixels \
+                or buf.device != self.device:
+            raise ValueError(f"a packed buffer of this batch holds {C} x {self.pixels} bf16 elements on {self.device}")
+
+    def view(self, buf, C, i):
+        """Item i of a packed C-channel buffer as a [1, C, h, w] view."""
+        h, w = self.shapes[i]
+        return buf[C * self.px_off[i]:C * (self.px_off[i] + h * w)].view(1, C, h, w)
+
+    def pack(self, images):
+        """A new packed buffer holding the [1, C, h, w] images (tests and tools)."""
+        C = images[0].shape[1]
+        buf = torch.empty(C * self.pixels, dtype=torch.bfloat16, device=self.device)
+        for i, im in enumerate(images):
+            self.view(buf, C, i).copy_(im)
+        return buf
+
+    def input(self, i):
+        return self.view(self.wide[0], self.CHANNELS, i)
+
+    def item_stats(self, st, i, C):
+        """Item i's header and partials of a batch statistics buffer, as the single call lays them out."""
+        at = self.stats_off[i] // 8
+        n = int(st[at:at + 1].view(torch.int64).item())
+        return st[at:at + 2 + C * n * 2]
+
+
 class HeadConvOps:
     """The head's convolutions on HIP (csrc/head_conv.hip): 1x1 and dilated 3x3 on the matrix cores,
     bf16 NCHW, with the InstanceNorm + ELU in front of a convolution applied as it loads its input
@@ -179,6 +286,55 @@ class HeadConvOps:
                                                    ctypes.c_float(eps), self._ptr(bias), self._ptr(out.get("scale")),
                                                    self._ptr(out.get("shift")), self._ptr(out.get("mean")),
                                                    self._stream()), "di_head_norm_fold")
+        return tuple(out[k] for k in want)
+
+
+    # ---- the same passes over a HeadBatch: one launch each, whatever the number of images ----
+    def conv_batch(self, hb, x, weight, y=None, bias=None, in_scale=None, in_shift=None, in_elu=False, dilation=1,
+                   stats=False):
+        """conv for every image of a HeadBatch: x a packed [Cin * pixels] buffer, y the packed output
+        (None: a new buffer), in_scale / in_shift [count, Cin] fp32 rows or None, weight / bias shared.
+        With stats=True the batch's statistics buffer is written (every item at its stats_off).
+        Returns y, or (y, hb.stats)."""
+        if weight.dtype != torch.bfloat16 or not weight.is_contiguous() or weight.dim() != 4:
+            raise ValueError("head conv weights are the module's contiguous bf16 [Cout, Cin, k, k] tensor")
+        cout, cin, k, _ = weight.shape
+        hb.check_packed(x, cin)
+        for v in (in_scale, in_shift):
+            if v is not None and (v.dtype != torch.float32 or not v.is_contiguous()
+                                  or tuple(v.shape) != (hb.count, cin)):
+                raise ValueError("the batch's scale / shift are contiguous fp32 [count, Cin] rows")
+        if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
+            raise ValueError("per-channel vectors are contiguous fp32")
+        if y is None:
+            y = torch.empty(cout * hb.pixels, dtype=torch.bfloat16, device=x.device)
+        hb.check_packed(y, cout)
+        args = self._lib.DiHeadConvArgs(x.data_ptr(), weight.data_ptr(), self._ptr(in_scale).value,
+                                        self._ptr(in_shift).value, self._ptr(bias).value, y.data_ptr(),
+                                        hb.stats.data_ptr() if stats else None, cin, cout, 0, 0, k, int(dilation),
+                                        int(bool(in_elu)))
+        self._lib.check(self.lib.di_head_conv_batch(self._lib.DI_BF16, ctypes.byref(args), hb.items, hb.items_ptr,
+                                                    hb.count, self._stream()), "di_head_conv_batch")
+        return (y, hb.stats) if stats else y
+
+    def plane_stats_batch(self, hb, x, C):
+        """The batch's statistics buffer of a packed C-channel buffer (one read pass)."""
+        hb.check_packed(x, C)
+        self._lib.check(self.lib.di_plane_stats_batch(self._lib.DI_BF16, self._ptr(x), C, hb.items, hb.items_ptr,
+                                                      hb.count, self._ptr(hb.stats), self._stream()),
+                        "di_plane_stats_batch")
+        return hb.stats
+
+    def fold_batch(self, hb, st, C, gamma=None, beta=None, eps=0.0, bias=None, want=("scale", "shift"), out=None):
+        """fold for every item of a batch statistics buffer: fp32 [count, C] rows. out: a dict of
+        preallocated rows by name (None: new tensors)."""
+        out = {k: (out[k] if out is not None else torch.empty(hb.count, C, dtype=torch.float32, device=st.device))
+               for k in want}
+        self._lib.check(self.lib.di_head_norm_fold_batch(self._ptr(st), C, hb.items, hb.items_ptr, hb.count,
+                                                         self._ptr(gamma), self._ptr(beta), ctypes.c_float(eps),
+                                                         self._ptr(bias), self._ptr(out.get("scale")),
+                                                         self._ptr(out.get("shift")), self._ptr(out.get("mean")),
+                                                         self._stream()), "di_head_norm_fold_batch")
         return tuple(out[k] for k in want)
 
 
@@ -305,6 +461,49 @@ class ResNet(nn.Module):
         return x
 
 
+    def _forward_hipconv_batch(self, hb, x, spare, ops, cops, in_elu=False):
+        """_forward_hipconv for every image of a HeadBatch at once: each pass is one launch over the
+        packed buffers, the SE gate one di_se_gate launch in fp32 (the single path's gate goes through
+        torch's bf16 linears). x: the packed residual stream; spare: the other 128-channel buffer.
+        Returns (the buffer holding the result, the free one)."""
+        m = self._modules
+        C = hb.CHANNELS
+        h1, h2 = hb.half
+        rows = dict(scale=hb.rows[0], shift=hb.rows[1], mean=hb.rows[2])
+        gate = hb.rows[3]
+        if self.initial_projection:
+            proj = m[f"resnet_{self.module_name}_init_proj"]
+            cops.conv_batch(hb, x, proj.weight, y=spare, bias=ops.f32(proj.bias), in_elu=in_elu)
+            x, spare = spare, x
+        elif in_elu:
+            raise NotImplementedError("a batched ResNet applies the caller's ELU in its initial projection")
+        for r in self.blocks:
+            st = cops.plane_stats_batch(hb, x, C) if self.inorm else None
+            t = x
+            for i, y in ((1, h1), (2, h2), (3, spare)):
+                conv = m[f"{r}_conv2d_{i}"]
+                cin = conv.weight.shape[1]
+                if self.inorm:
+                    norm = m[f"{r}_inorm_{i}"]
+                    # [count, cin] rows: contiguous views of the batch's [count, C] storage
+                    out = {k: rows[k].view(-1)[:hb.count * cin].view(hb.count, cin) for k in ("scale", "shift")}
+                    sc, sh = cops.fold_batch(hb, st, cin, ops.f32(norm.weight), ops.f32(norm.bias), norm.eps, out=out)
+                    _, st = cops.conv_batch(hb, t, conv.weight, y=y, in_scale=sc, in_shift=sh, in_elu=True,
+                                            dilation=conv.dilation[0], stats=True)
+                elif i < 3:
+                    cops.conv_batch(hb, t, conv.weight, y=y, bias=ops.f32(conv.bias), in_elu=True,
+                                    dilation=conv.dilation[0])
+                else:
+                    _, st = cops.conv_batch(hb, t, conv.weight, y=y, in_elu=True, stats=True)
+                t = y
+            conv3, se = m[f"{r}_conv2d_3"], m[f"{r}_se_block"]
+            (mean,) = cops.fold_batch(hb, st, C, bias=ops.f32(conv3.bias), want=("mean",), out=rows)
+            ops.se_gate(se, mean, out=gate)
+            ops.se_scale_add_batch(hb, spare, gate, x, out=spare, bias=conv3.bias)
+            x, spare = spare, x
+        return x, spare
+
+
 class ResNet2DInputWithOptAttention(nn.Module):
     def __init__(self, num_chunks=14, init_channels=256, num_channels=128, num_classes=2):
         super().__init__()
@@ -347,6 +546,24 @@ class ResNet2DInputWithOptAttention(nn.Module):
         x = F.elu(self.base_resnet(x))
         x = F.elu(self.phase2_resnet(x))
         return self.phase2_conv(x)
+
+
+    def body_batch(self, xs):
+        """body for several images in one launch sequence (bf16, HIP convolutions): xs is a list of
+        [1, 128, h, w] prologue outputs, or a HeadBatch whose ``input(i)`` views hold them. Returns
+        the list of logits. Each image's logits are the same bits whatever else the batch holds."""
+        if getattr(self, "cops", None) is None or self.ops is None:
+            raise RuntimeError("body_batch needs the HIP convolutions and norm passes (use_hip_convs, "
+                               "use_hip_norm_ops)")
+        if isinstance(xs, HeadBatch):
+            hb = xs
+        else:
+            hb = HeadBatch([x.shape[2:] for x in xs], xs[0].device)
+            for i, x in enumerate(xs):
+                hb.input(i).copy_(x)
+        x, spare = self.base_resnet._forward_hipconv_batch(hb, hb.wide[0], hb.wide[1], self.ops, self.cops)
+        x, spare = self.phase2_resnet._forward_hipconv_batch(hb, x, spare, self.ops, self.cops, in_elu=True)
+        return [self.phase2_conv(F.elu(hb.view(x, hb.CHANNELS, i))) for i in range(hb.count)]
 
 
 def contact_probs(logits):

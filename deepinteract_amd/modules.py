@@ -24,7 +24,7 @@ import torch.nn as nn
 from .config import GeoTConfig, NODE_COUNT_LIMIT, RESIDUE_COUNT_LIMIT
 from .engine import GeoTEngine, HeadPrologueOp, PairTensorOp, gpu_device
 from .graph import GraphBatch, ResidueGraph, batch as batch_graphs, unbatch
-from .head import HeadConvOps, HeadNormOps, ResNet2DInputWithOptAttention, contact_probs
+from .head import HeadBatch, HeadConvOps, HeadNormOps, ResNet2DInputWithOptAttention, contact_probs
 from .ranking import (ContactAucOp, ContactRankOp, confusion_metrics, labels_from_examples,
                       labels_from_examples_batch, topk_metrics)
 
@@ -87,7 +87,7 @@ class LitGINI(nn.Module):
                  num_classes=2, max_num_graph_nodes=NODE_COUNT_LIMIT, max_num_residues=RESIDUE_COUNT_LIMIT,
                  dtype="f32", head_dtype=torch.float32, precise_head=False, fuse_head_prologue=False,
                  head_channels_last=False, head_hip_ops=True, head_convs="torch", pos_prob_threshold=0.5,
-                 **kwargs):
+                 head_batch=0, head_batch_pixels=2 ** 22, **kwargs):
         super().__init__()
         if num_gnn_hidden_channels != 128 or num_gnn_attention_heads != 4:
             # Q/K/V are Linear(H, H) whatever the head count, so a checkpoint trained with another
@@ -127,6 +127,16 @@ class LitGINI(nn.Module):
             raise ValueError('head_convs="hip" needs head_dtype=torch.bfloat16, head_hip_ops=True and no '
                              "head_channels_last")
         self.head_convs = head_convs
+        # head_batch: N > 0 sends _forward_batch's complexes through the head's blocks in chunks of at
+        # most N complexes and at most head_batch_pixels pixels (L1 * L2 summed), every head kernel
+        # launched once per chunk (head.HeadBatch, body_batch). The chunk's arena takes 768 B per
+        # pixel, so the default cap keeps it at 3 GiB; a complex larger than the cap goes alone.
+        head_batch, head_batch_pixels = int(head_batch), int(head_batch_pixels)
+        if head_batch < 0 or head_batch_pixels < 1:
+            raise ValueError("head_batch must be >= 0 and head_batch_pixels >= 1")
+        if head_batch > 0 and head_convs != "hip":
+            raise ValueError('head_batch > 0 needs head_convs="hip" (the batched head runs on the HIP convolutions)')
+        self.head_batch, self.head_batch_pixels = head_batch, head_batch_pixels
         self.max_num_residues = max_num_residues
         # pos_prob_threshold: a contact is predicted where its probability reaches it (test_step's
         # rounded predictions and confusion counts; the reference's default)
@@ -198,7 +208,8 @@ class LitGINI(nn.Module):
             raise RuntimeError(f"{checkpoint_path}: state dict does not match LitGINI ({len(problems)} problems): "
                                + "; ".join(problems[:8]))
         opts = {k: kwargs[k] for k in ("dtype", "head_dtype", "precise_head", "fuse_head_prologue",
-                                       "head_channels_last", "head_hip_ops", "head_convs") if k in kwargs}
+                                       "head_channels_last", "head_hip_ops", "head_convs", "head_batch",
+                                       "head_batch_pixels") if k in kwargs}
         model = cls(num_node_input_feats=cfg.num_node_input_feats, num_gnn_layers=cfg.num_gnn_layers,
                     num_gnn_hidden_channels=cfg.num_gnn_hidden_channels,
                     num_gnn_attention_heads=cfg.num_gnn_attention_heads, knn=cfg.knn,
@@ -268,11 +279,44 @@ class LitGINI(nn.Module):
         l2 = [gb.nodes_per_graph[b] for _, b in pairs]
         if prologue_op is not None:
             _, views = prologue_op(h, h1r, h2r, l1, l2)
-            logits = [self.interact_forward(v, prologue_done=True) for v in views]
+            logits = self._head_batched(views, True) if self.head_batch > 0 else \
+                [self.interact_forward(v, prologue_done=True) for v in views]
         else:
             _, views = pair_op(h, h1r, h2r, l1, l2, hT=eng.last_hT)
-            logits = [self.interact_forward(v) for v in views]
+            logits = self._head_batched(views, False) if self.head_batch > 0 else \
+                [self.interact_forward(v) for v in views]
         return logits, h, e
+
+    def _head_chunks(self, shapes):
+        """Consecutive complexes in chunks of at most head_batch complexes and head_batch_pixels pixels."""
+        chunks, cur, px = [], [], 0
+        for i, (a, b) in enumerate(shapes):
+            if cur and (len(cur) == self.head_batch or px + a * b > self.head_batch_pixels):
+                chunks.append(cur)
+                cur, px = [], 0
+            cur.append(i)
+            px += a * b
+        if cur:
+            chunks.append(cur)
+        return chunks
+
+    def _head_batched(self, views, prologue_done):
+        """The head over the complexes' views chunk by chunk (head_batch > 0): the prologue per complex,
+        written straight into the chunk's arena, then the blocks once for the whole chunk."""
+        import contextlib
+        im = self.interact_module
+        logits = []
+        # precise_head: conv2d_1 and phase2_conv (the two convolutions left on torch) as interact_forward
+        with torch.backends.cudnn.flags(enabled=False) if self.precise_head else contextlib.nullcontext():
+            for chunk in self._head_chunks([tuple(v.shape[2:]) for v in views]):
+                hb = HeadBatch([views[i].shape[2:] for i in chunk], views[chunk[0]].device)
+                for slot, i in enumerate(chunk):
+                    if prologue_done:
+                        hb.input(slot).copy_(views[i])
+                    else:
+                        im.ops.inorm_elu(im.conv2d_1(views[i].to(self.head_dtype)), im.inorm_1, out=hb.input(slot))
+                logits += im.body_batch(hb)
+        return logits
 
     def predict_batch(self, gb: GraphBatch, pairs):
         """pairs: (chain-1 graph index, chain-2 graph index) per complex -> (logits, probs)."""

@@ -388,6 +388,53 @@ int di_plane_stats(di_dtype dt, const void* x, int32_t channels, int64_t hw, voi
 int di_head_norm_fold(const void* stats, int32_t channels, int64_t hw, const float* gamma, const float* beta,
                       float eps, const float* bias, float* scale, float* shift, float* mean, void* stream);
 
+/* ---- the contact-head body over a ragged batch of images (an addition to ABI 8) -------------
+ * `count` images of different shapes go through each head kernel in ONE launch, whatever count is.
+ * Packed ragged image: a batch of [C, h_i, w_i] bf16 images in one buffer, item i a contiguous NCHW
+ * image at element offset C * px_off_i, px_off_i = sum over j < i of h_j * w_j (64-bit). The head's C
+ * are multiples of 64, so with a 128-B aligned buffer every item starts 128-B aligned.
+ * di_head_batch_layout fills px_off and stats_off (the item's byte offset in the batch's statistics
+ * buffer: 16-B aligned, room for di_head_conv_stats_bytes(128, h, w)) from h and w, and returns the
+ * pixel total and the statistics buffer's bytes through total_px / stats_bytes. One table serves every
+ * launch of a forward:
+ *   items      host array [count]: validated, and used for grid sizes; may be freed on return
+ *   items_dev  a copy of it in device memory, made by the caller (in stream order before the call;
+ *              it must stay unchanged until the call's kernels have run)
+ * The grid's z index names the item; a block reads its item from the device table, leaves as a whole
+ * (before any barrier) when its x / y index lies past that item's own tile or slice count, and
+ * otherwise runs the single call's code on that item's sizes alone: every output of an item (the
+ * statistics partials included) has the bits the single call gives on that image.
+ * di_head_conv_batch: args as di_head_conv with x, y and stats packed buffers (stats nullable),
+ * in_scale / in_shift [count, cin] fp32 rows (nullable), weight and bias shared; args->h and args->w
+ * are ignored. di_plane_stats_batch: bf16 only, x 16-B aligned, channels a multiple of 8 (items start
+ * 16-B aligned) and <= 128 (an item's room in stats). di_head_norm_fold_batch: channels <= 128; gamma,
+ * beta, bias [channels] shared; scale / shift / mean [count, channels] rows, each nullable.
+ * di_se_scale_add_batch: scale [count, channels], bias [channels] (nullable); bf16, 16-B aligned,
+ * channels a multiple of 8; y may alias x or res.
+ * di_se_gate: gate[i][c] = sigmoid(relu(b2[c] + sum_j w2[c][j] * relu(b1[j] + sum_k w1[j][k] *
+ * mean[i][k]))) -- SEBlock's two linears (deepinteract_modules.py:954-970) on [count, channels] fp32
+ * means, all fp32, each sum taken in index order by fused multiply-adds starting from the bias, so a
+ * row's bits depend on nothing but that row. w1 [hidden, channels], w2 [channels, hidden] row-major.
+ * channels 1 .. 1024, hidden 1 .. 64, count >= 1. One launch.
+ * Asynchronous, no allocation, every refusal before any launch. DI_EINVAL: count < 1, a NULL table,
+ * h or w < 1, offsets that the helper did not fill, or anything the single call refuses with
+ * DI_EINVAL; DI_ERANGE: count > DI_BATCH_MAX, more than 2^40 pixels in all, or an item the single
+ * call refuses with DI_ERANGE. */
+typedef struct { int64_t px_off, stats_off; int32_t h, w; } di_head_item;
+int di_head_batch_layout(di_head_item* items, int32_t count, int64_t* total_px, int64_t* stats_bytes);
+int di_head_conv_batch(di_dtype dt, const di_head_conv_args* args, const di_head_item* items,
+                       const di_head_item* items_dev, int32_t count, void* stream);
+int di_plane_stats_batch(di_dtype dt, const void* x, int32_t channels, const di_head_item* items,
+                         const di_head_item* items_dev, int32_t count, void* stats, void* stream);
+int di_head_norm_fold_batch(const void* stats, int32_t channels, const di_head_item* items,
+                            const di_head_item* items_dev, int32_t count, const float* gamma, const float* beta,
+                            float eps, const float* bias, float* scale, float* shift, float* mean, void* stream);
+int di_se_scale_add_batch(di_dtype dt, const void* x, const float* scale, const float* bias, const void* res,
+                          int32_t channels, const di_head_item* items, const di_head_item* items_dev,
+                          int32_t count, void* y, void* stream);
+int di_se_gate(const float* mean, const float* w1, const float* b1, const float* w2, const float* b2,
+               int32_t count, int32_t channels, int32_t hidden, float* gate, void* stream);
+
 /* ---- contact ranking (an addition to ABI 8) ------------------------------------------------
  * What LitGINI.test_step does with one complex's logits (deepinteract_modules.py:2018-2101; top-k
  * precision / recall deepinteract_utils.py:977-995), without sorting the map. logits: [1, 2, l1, l2]
