@@ -26,8 +26,9 @@
 //        product over the halo shifted by (ty d, tx d): a dilated 3x3 is nine shifted 1x1 products.
 //        Three instantiations by LDS size (d <= 2, <= 4, <= 8: 63 / 74 / 102 KiB for Cout = 64).
 // Plane offsets (channel * hw) are 64-bit. Ordinary launches; no block waits for another.
-// di_head_conv_batch runs the same block code over a packed ragged batch of images in one launch
-// (k_head_conv_batch below; the layout and the item table: include/deepinteract_amd.h).
+// di_head_conv_batch runs the same kernel over a packed ragged batch of images in one launch (given the
+// batch's item table, a block of k_head_conv rebases its pointers and takes h / w from its item; the
+// layout and the item table: include/deepinteract_amd.h).
 //
 // Statistics (optional): per output channel (sum y, sum y^2) of the values AS STORED (after the bf16
 // rounding). A thread sums its 4 pixels in fp32 (as k_inorm_stats sums a vector's elements); from
@@ -101,9 +102,9 @@ constexpr int hc_blocks_per_cu(int ks, int cout, int dmax) {
   return ks == 1 || (cout == 64 && dmax <= 4) ? 2 : 1;
 }
 
-// One block's work, for block (bx, by) of an image's own gx x gy grid (1x1: gy = 1). The single call's
-// kernel and the batch's both run exactly this, so an image's output and statistics partials do not
-// depend on which of the two launched it.
+// One block's work, for block (bx, by) of an image's own gx x gy grid (1x1: gy = 1). A single call and a
+// batch both run exactly this, so an image's output and statistics partials do not depend on which of
+// the two launched it.
 template <int KS, int COUT, int DMAX>
 __device__ __forceinline__ void head_conv_body(const HcArgs& a, const int bx, const int by, const int gx,
                                                const int gy) {
@@ -291,43 +292,44 @@ __device__ __forceinline__ void head_conv_body(const HcArgs& a, const int bx, co
   }
 }
 
-template <int KS, int COUT, int DMAX>
-__global__ __launch_bounds__(HC_THREADS, hc_blocks_per_cu(KS, COUT, DMAX)) void k_head_conv(const HcArgs a) {
-  head_conv_body<KS, COUT, DMAX>(a, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
-}
-
-// The batch: blockIdx.z names the item, the x / y grid is the largest item's, and a block past its own
-// item's tile count leaves at once -- as a whole, before any barrier. (The project's idiom, as the
-// rank / AUC batches: against a prefix table of tiles it needs no second table and no search per
-// block, and a block that only reads its item and leaves costs far less than the launch it saves; a
-// batch of one large and many small images starts at most (count - 1) x the large one's tiles of them.)
-// a.x, a.y, a.stats, a.in_scale, a.in_shift are the packed buffers' bases; h, wd, hw are unused.
-template <int KS, int COUT, int DMAX>
-__global__ __launch_bounds__(HC_THREADS, hc_blocks_per_cu(KS, COUT, DMAX)) void k_head_conv_batch(
-    const HcArgs a, const di_head_item* __restrict__ items) {
-  const int z = blockIdx.z;
-  const int h = items[z].h, wd = items[z].w;
-  const int64_t hw = (int64_t)h * wd;
+// One kernel serves the single call and the batch. For a single call (TABLE = false, items unused) it
+// uses `a` as the host filled it. For a batch, blockIdx.z names the item: a.x, a.y, a.stats, a.in_scale
+// and a.in_shift are the packed buffers' bases, which the block rebases to its item, and h, wd, hw come
+// from the item; the x / y grid is the largest item's, and a block past its own item's tile count leaves
+// at once -- as a whole, before any barrier. (The project's idiom, as the rank / AUC batches: against a
+// prefix table of tiles it needs no second table and no search per block, and a block that only reads
+// its item and leaves costs far less than the launch it saves; a batch of one large and many small
+// images starts at most (count - 1) x the large one's tiles of them.) The image's own grid gx x gy comes
+// from h / wd / hw in both cases (in a single call it is the launch's grid, so no block leaves).
+// TABLE is a template parameter -- the call kind is known where the launch is written -- and not a test
+// of `items`: behind such a test the single call loads its arguments in two dependent rounds (the
+// table pointer, a branch, then the rest), and the whole head at 1000 x 1000 measured 0.1 - 0.2 % slower,
+// just outside the window of the kernels before the merge.
+template <int KS, int COUT, int DMAX, bool TABLE>
+__global__ __launch_bounds__(HC_THREADS, hc_blocks_per_cu(KS, COUT, DMAX)) void k_head_conv(
+    HcArgs a, const di_head_item* __restrict__ items) {
+  if constexpr (TABLE) {
+    const int z = blockIdx.z;
+    const int64_t px = items[z].px_off;
+    a.h = items[z].h;
+    a.wd = items[z].w;
+    a.hw = (int64_t)a.h * a.wd;
+    a.x += (int64_t)a.cin * px;
+    a.y += (int64_t)COUT * px;
+    a.stats = a.stats ? reinterpret_cast<double*>(reinterpret_cast<char*>(a.stats) + items[z].stats_off) : nullptr;
+    a.in_scale = a.in_scale ? a.in_scale + (int64_t)z * a.cin : nullptr;
+    a.in_shift = a.in_shift ? a.in_shift + (int64_t)z * a.cin : nullptr;
+  }
   int gx, gy;
   if constexpr (KS == 3) {
-    gx = (wd + HC_TILE - 1) / HC_TILE;
-    gy = (h + HC_TILE - 1) / HC_TILE;
+    gx = (a.wd + HC_TILE - 1) / HC_TILE;
+    gy = (a.h + HC_TILE - 1) / HC_TILE;
   } else {
-    gx = (int)((hw + HC_PIX - 1) / HC_PIX);
+    gx = (int)((a.hw + HC_PIX - 1) / HC_PIX);
     gy = 1;
   }
-  if ((int)blockIdx.x >= gx || (int)blockIdx.y >= gy) return;
-  const int64_t px = items[z].px_off;
-  HcArgs b = a;
-  b.x = a.x + (int64_t)a.cin * px;
-  b.y = a.y + (int64_t)COUT * px;
-  b.stats = a.stats ? reinterpret_cast<double*>(reinterpret_cast<char*>(a.stats) + items[z].stats_off) : nullptr;
-  b.in_scale = a.in_scale ? a.in_scale + (int64_t)z * a.cin : nullptr;
-  b.in_shift = a.in_shift ? a.in_shift + (int64_t)z * a.cin : nullptr;
-  b.hw = hw;
-  b.h = h;
-  b.wd = wd;
-  head_conv_body<KS, COUT, DMAX>(b, blockIdx.x, blockIdx.y, gx, gy);
+  if (TABLE && ((int)blockIdx.x >= gx || (int)blockIdx.y >= gy)) return;
+  head_conv_body<KS, COUT, DMAX>(a, blockIdx.x, blockIdx.y, gx, gy);
 }
 
 // blocks of a launch = partials per channel
@@ -351,28 +353,48 @@ static int hc_check(di_dtype dt, const di_head_conv_args* a) {
   return DI_OK;
 }
 
-template <int KS, int COUT, int DMAX>
-static void hc_launch(const HcArgs& k, dim3 grid, hipStream_t s, const di_head_item* items = nullptr) {
-  if (items) hipLaunchKernelGGL((k_head_conv_batch<KS, COUT, DMAX>), grid, dim3(HC_THREADS), 0, s, k, items);
-  else hipLaunchKernelGGL((k_head_conv<KS, COUT, DMAX>), grid, dim3(HC_THREADS), 0, s, k);
+template <int KS, int COUT, int DMAX, bool TABLE>
+static void hc_launch(const HcArgs& k, dim3 grid, hipStream_t s, const di_head_item* items) {
+  hipLaunchKernelGGL((k_head_conv<KS, COUT, DMAX, TABLE>), grid, dim3(HC_THREADS), 0, s, k, items);
 }
 
-// the instantiation for (ksize, cout, dilation); items: the batch's device table, or NULL
+// the kernel's arguments from the call's, for an image of h x w pixels (a batch: 0 x 0, every block
+// takes its item's)
+static HcArgs hc_args(const di_head_conv_args* args, int32_t h, int32_t w) {
+  HcArgs k;
+  k.x = (const u16*)args->x;
+  k.w = (const u16*)args->weight;
+  k.in_scale = args->in_scale;
+  k.in_shift = args->in_shift;
+  k.bias = args->bias;
+  k.y = (u16*)args->y;
+  k.stats = (double*)args->stats;
+  k.hw = (int64_t)h * w;
+  k.cin = args->cin;
+  k.h = h;
+  k.wd = w;
+  k.dil = args->dilation;
+  k.in_elu = args->in_elu ? 1 : 0;
+  return k;
+}
+
+// the instantiation for (ksize, cout, dilation); items: the batch's device table (TABLE), or NULL
+template <bool TABLE>
 static void hc_dispatch(const HcArgs& k, int ksize, int cout, int d, dim3 grid, hipStream_t s,
-                        const di_head_item* items = nullptr) {
+                        const di_head_item* items) {
   const bool wide = cout == 128;
   if (ksize == 1) {
-    if (wide) hc_launch<1, 128, 0>(k, grid, s, items);
-    else hc_launch<1, 64, 0>(k, grid, s, items);
+    if (wide) hc_launch<1, 128, 0, TABLE>(k, grid, s, items);
+    else hc_launch<1, 64, 0, TABLE>(k, grid, s, items);
   } else if (d <= 2) {
-    if (wide) hc_launch<3, 128, 2>(k, grid, s, items);
-    else hc_launch<3, 64, 2>(k, grid, s, items);
+    if (wide) hc_launch<3, 128, 2, TABLE>(k, grid, s, items);
+    else hc_launch<3, 64, 2, TABLE>(k, grid, s, items);
   } else if (d <= 4) {
-    if (wide) hc_launch<3, 128, 4>(k, grid, s, items);
-    else hc_launch<3, 64, 4>(k, grid, s, items);
+    if (wide) hc_launch<3, 128, 4, TABLE>(k, grid, s, items);
+    else hc_launch<3, 64, 4, TABLE>(k, grid, s, items);
   } else {
-    if (wide) hc_launch<3, 128, 8>(k, grid, s, items);
-    else hc_launch<3, 64, 8>(k, grid, s, items);
+    if (wide) hc_launch<3, 128, 8, TABLE>(k, grid, s, items);
+    else hc_launch<3, 64, 8, TABLE>(k, grid, s, items);
   }
 }
 
@@ -395,24 +417,10 @@ extern "C" int64_t di_head_conv_stats_bytes(int32_t cout, int32_t h, int32_t w) 
 extern "C" int di_head_conv(di_dtype dt, const di_head_conv_args* args, void* stream) {
   const int rc = hc_check(dt, args);
   if (rc != DI_OK) return rc;
-  HcArgs k;
-  k.x = (const u16*)args->x;
-  k.w = (const u16*)args->weight;
-  k.in_scale = args->in_scale;
-  k.in_shift = args->in_shift;
-  k.bias = args->bias;
-  k.y = (u16*)args->y;
-  k.stats = (double*)args->stats;
-  k.hw = (int64_t)args->h * args->w;
-  k.cin = args->cin;
-  k.h = args->h;
-  k.wd = args->w;
-  k.dil = args->dilation;
-  k.in_elu = args->in_elu ? 1 : 0;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid = args->ksize == 1 ? dim3((unsigned)hc_blocks(1, args->h, args->w))
                                      : dim3((args->w + HC_TILE - 1) / HC_TILE, (args->h + HC_TILE - 1) / HC_TILE);
-  hc_dispatch(k, args->ksize, args->cout, args->dilation, grid, s);
+  hc_dispatch<false>(hc_args(args, args->h, args->w), args->ksize, args->cout, args->dilation, grid, s, nullptr);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
 }
@@ -455,21 +463,8 @@ extern "C" int di_head_conv_batch(di_dtype dt, const di_head_conv_args* args, co
     gx = ix > gx ? ix : gx;
     gy = iy > gy ? iy : gy;
   }
-  HcArgs k;
-  k.x = (const u16*)args->x;
-  k.w = (const u16*)args->weight;
-  k.in_scale = args->in_scale;
-  k.in_shift = args->in_shift;
-  k.bias = args->bias;
-  k.y = (u16*)args->y;
-  k.stats = (double*)args->stats;
-  k.hw = 0;
-  k.cin = args->cin;
-  k.h = 0;
-  k.wd = 0;
-  k.dil = args->dilation;
-  k.in_elu = args->in_elu ? 1 : 0;
-  hc_dispatch(k, args->ksize, args->cout, args->dilation, dim3(gx, gy, (unsigned)count), (hipStream_t)stream, items_dev);
+  hc_dispatch<true>(hc_args(args, 0, 0), args->ksize, args->cout, args->dilation, dim3(gx, gy, (unsigned)count),
+              (hipStream_t)stream, items_dev);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
 }

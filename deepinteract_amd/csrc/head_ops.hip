@@ -19,7 +19,9 @@
 //    a convolution's epilogue -- into the per-channel scale / shift the next convolution applies as it
 //    loads, or into the SE squeeze.
 //  * di_plane_stats_batch / di_head_norm_fold_batch / di_se_scale_add_batch: the same passes over a
-//    packed ragged batch of images, one launch each, every image with the single call's decomposition
+//    packed ragged batch of images, one launch each of the SAME kernels (k_inorm_stats, k_head_norm_fold,
+//    k_se_scale_add: instantiated for a batch, a block rebases its pointers and takes hw from its item
+//    of the table; for a single call it uses its arguments as given), every image with the single call's decomposition
 //    and bits; di_se_gate: SEBlock's two linears, ReLU and sigmoid for the batch's means, in fp32.
 // The convs before an InstanceNorm run without their bias (a per-channel constant cancels in
 // the normalisation exactly), so the head does no separate bias-add passes.
@@ -113,8 +115,8 @@ __host__ __device__ static inline int ho_split(int channels, int64_t hw, int vec
   return split;
 }
 
-// Slice bx of the `split` slices of channel c's plane. The single kernels and the batch's run these
-// bodies, an image's own split and sizes in hand, so both give an image the same bits.
+// Slice bx of the `split` slices of channel c's plane. A single call and a batch run these bodies, an
+// image's own split and sizes in hand, so both give an image the same bits.
 template <typename T>
 __device__ __forceinline__ void inorm_stats_body(const T* __restrict__ x, int64_t hw, double* __restrict__ part,
                                                  int64_t* __restrict__ hdr, const int c, const int split,
@@ -169,11 +171,30 @@ __device__ __forceinline__ void inorm_stats_body(const T* __restrict__ x, int64_
   }
 }
 
-template <typename T>
+// The batch (TABLE; blockIdx.z = item; see k_head_conv): an item's planes start at channels * px_off
+// elements, 128-B aligned, so Plane splits them as the single call does with the item as its buffer; the
+// slice count is the single call's for that item's hw, and blocks past it leave before any barrier. A
+// single call (TABLE = false, items unused) uses its arguments as given: the grid's x size is its split.
+// The three kernels that serve both follow this form; TABLE is a template parameter, not a test of
+// `items`, for the reason given at k_head_conv.
+//
+// hdr: nullptr (partials only, to part), or the statistics buffer: the header, the partials behind it;
+// for a batch the buffer's base, every item's at its stats_off.
+template <typename T, bool TABLE>
 __global__ __launch_bounds__(HO_THREADS) void k_inorm_stats(const T* __restrict__ x, int64_t hw,
-                                                            double* __restrict__ part,
-                                                            int64_t* __restrict__ hdr = nullptr) {
-  inorm_stats_body<T>(x, hw, part, hdr, blockIdx.y, gridDim.x, blockIdx.x);
+                                                            double* __restrict__ part, int64_t* __restrict__ hdr,
+                                                            int channels, const di_head_item* __restrict__ items) {
+  int split = gridDim.x;
+  if constexpr (TABLE) {
+    const di_head_item it = items[blockIdx.z];
+    hw = (int64_t)it.h * it.w;
+    split = ho_split(channels, hw, Vec<T>::N);
+    if ((int)blockIdx.x >= split) return;
+    x += (int64_t)channels * it.px_off;
+    hdr = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(hdr) + it.stats_off);
+    part = reinterpret_cast<double*>(hdr) + 2;
+  }
+  inorm_stats_body<T>(x, hw, part, hdr, blockIdx.y, split, blockIdx.x);
 }
 
 __device__ __forceinline__ float elu1(float z) { return z > 0.f ? z : expm1f(z); }
@@ -254,41 +275,23 @@ __device__ __forceinline__ void se_scale_add_body(const T* __restrict__ x, const
   }
 }
 
-template <typename T>
+template <typename T, bool TABLE>
 __global__ __launch_bounds__(HO_THREADS) void k_se_scale_add(const T* __restrict__ x, const float* __restrict__ s,
                                                              const float* __restrict__ bias,
                                                              const T* __restrict__ res, int64_t hw,
-                                                             T* __restrict__ y) {
-  se_scale_add_body<T>(x, s, bias, res, hw, y, blockIdx.y, gridDim.x, blockIdx.x);
-}
-
-// The batch (blockIdx.z = item; see k_head_conv_batch): an item's planes start at channels * px_off
-// elements, 128-B aligned, so Plane splits them as the single call does with the item as its buffer;
-// the slice count is the single call's for that item's hw, and blocks past it leave before any barrier.
-__global__ __launch_bounds__(HO_THREADS) void k_plane_stats_batch(const u16* __restrict__ x, int channels,
-                                                                  const di_head_item* __restrict__ items,
-                                                                  char* __restrict__ stats) {
-  const di_head_item it = items[blockIdx.z];
-  const int64_t hw = (int64_t)it.h * it.w;
-  const int split = ho_split(channels, hw, 8);
-  if ((int)blockIdx.x >= split) return;
-  int64_t* hdr = reinterpret_cast<int64_t*>(stats + it.stats_off);
-  inorm_stats_body<u16>(x + (int64_t)channels * it.px_off, hw, reinterpret_cast<double*>(hdr) + 2, hdr, blockIdx.y,
-                        split, blockIdx.x);
-}
-
-__global__ __launch_bounds__(HO_THREADS) void k_se_scale_add_batch(const u16* __restrict__ x,
-                                                                   const float* __restrict__ s,
-                                                                   const float* __restrict__ bias,
-                                                                   const u16* __restrict__ res, int channels,
-                                                                   const di_head_item* __restrict__ items,
-                                                                   u16* __restrict__ y) {
-  const di_head_item it = items[blockIdx.z];
-  const int64_t hw = (int64_t)it.h * it.w, off = (int64_t)channels * it.px_off;
-  const int split = ho_split(channels, hw, 8);
-  if ((int)blockIdx.x >= split) return;
-  se_scale_add_body<u16>(x + off, s + (int64_t)blockIdx.z * channels, bias, res + off, hw, y + off, blockIdx.y, split,
-                         blockIdx.x);
+                                                             T* __restrict__ y, int channels,
+                                                             const di_head_item* __restrict__ items) {
+  int split = gridDim.x;
+  if constexpr (TABLE) {  // s: [count, channels] rows
+    const di_head_item it = items[blockIdx.z];
+    hw = (int64_t)it.h * it.w;
+    split = ho_split(channels, hw, Vec<T>::N);
+    if ((int)blockIdx.x >= split) return;
+    const int64_t off = (int64_t)channels * it.px_off;
+    x += off, res += off, y += off;
+    s += (int64_t)blockIdx.z * channels;
+  }
+  se_scale_add_body<T>(x, s, bias, res, hw, y, blockIdx.y, split, blockIdx.x);
 }
 
 // mean[c] = sum of the channel's partials / hw (+ bias[c]): SEBlock's x.mean(dim=(2, 3)) of a
@@ -338,28 +341,24 @@ __device__ __forceinline__ void head_norm_fold_body(const double* __restrict__ s
     if (mean) mean[c] = (float)(m + (bias ? (double)bias[c] : 0.0));
   }
 }
+template <bool TABLE>
 __global__ __launch_bounds__(HO_THREADS) void k_head_norm_fold(const double* __restrict__ stats, int64_t hw,
                                                                const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, float eps,
                                                                const float* __restrict__ bias,
                                                                float* __restrict__ scale, float* __restrict__ shift,
-                                                               float* __restrict__ mean) {
+                                                               float* __restrict__ mean, int channels,
+                                                               const di_head_item* __restrict__ items) {
+  if constexpr (TABLE) {  // grid (channels, count): item blockIdx.y's buffer into row blockIdx.y of scale / shift / mean
+    const di_head_item it = items[blockIdx.y];
+    const int64_t row = (int64_t)blockIdx.y * channels;
+    stats = reinterpret_cast<const double*>(reinterpret_cast<const char*>(stats) + it.stats_off);
+    hw = (int64_t)it.h * it.w;
+    scale = scale ? scale + row : nullptr;
+    shift = shift ? shift + row : nullptr;
+    mean = mean ? mean + row : nullptr;
+  }
   head_norm_fold_body(stats, hw, gamma, beta, eps, bias, scale, shift, mean, blockIdx.x);
-}
-// grid (channels, count): item blockIdx.y's buffer into row blockIdx.y of scale / shift / mean
-__global__ __launch_bounds__(HO_THREADS) void k_head_norm_fold_batch(const char* __restrict__ stats, int channels,
-                                                                     const di_head_item* __restrict__ items,
-                                                                     const float* __restrict__ gamma,
-                                                                     const float* __restrict__ beta, float eps,
-                                                                     const float* __restrict__ bias,
-                                                                     float* __restrict__ scale,
-                                                                     float* __restrict__ shift,
-                                                                     float* __restrict__ mean) {
-  const di_head_item it = items[blockIdx.y];
-  const int64_t row = (int64_t)blockIdx.y * channels;
-  head_norm_fold_body(reinterpret_cast<const double*>(stats + it.stats_off), (int64_t)it.h * it.w, gamma, beta, eps,
-                      bias, scale ? scale + row : nullptr, shift ? shift + row : nullptr, mean ? mean + row : nullptr,
-                      blockIdx.x);
 }
 
 // SEBlock's gate for `count` rows of means, one block per row: the hidden units by one thread each
@@ -410,11 +409,13 @@ extern "C" int di_inorm_elu(di_dtype dt, const void* x, int32_t channels, int64_
   hipStream_t s = (hipStream_t)stream;
   double* part = reinterpret_cast<double*>(work);
   if (dt == DI_BF16) {
-    hipLaunchKernelGGL(k_inorm_stats<u16>, grid, dim3(HO_THREADS), 0, s, (const u16*)x, hw, part);
+    hipLaunchKernelGGL((k_inorm_stats<u16, false>), grid, dim3(HO_THREADS), 0, s, (const u16*)x, hw, part, nullptr, channels,
+                       nullptr);
     hipLaunchKernelGGL(k_inorm_apply<u16>, grid, dim3(HO_THREADS), 0, s, (const u16*)x, hw, part, gamma, beta,
                        eps, (u16*)y);
   } else {
-    hipLaunchKernelGGL(k_inorm_stats<float>, grid, dim3(HO_THREADS), 0, s, (const float*)x, hw, part);
+    hipLaunchKernelGGL((k_inorm_stats<float, false>), grid, dim3(HO_THREADS), 0, s, (const float*)x, hw, part, nullptr, channels,
+                       nullptr);
     hipLaunchKernelGGL(k_inorm_apply<float>, grid, dim3(HO_THREADS), 0, s, (const float*)x, hw, part, gamma,
                        beta, eps, (float*)y);
   }
@@ -431,9 +432,11 @@ extern "C" int di_channel_mean(di_dtype dt, const void* x, int32_t channels, int
   hipStream_t s = (hipStream_t)stream;
   double* part = reinterpret_cast<double*>(work);
   if (dt == DI_BF16)
-    hipLaunchKernelGGL(k_inorm_stats<u16>, grid, dim3(HO_THREADS), 0, s, (const u16*)x, hw, part);
+    hipLaunchKernelGGL((k_inorm_stats<u16, false>), grid, dim3(HO_THREADS), 0, s, (const u16*)x, hw, part, nullptr, channels,
+                       nullptr);
   else
-    hipLaunchKernelGGL(k_inorm_stats<float>, grid, dim3(HO_THREADS), 0, s, (const float*)x, hw, part);
+    hipLaunchKernelGGL((k_inorm_stats<float, false>), grid, dim3(HO_THREADS), 0, s, (const float*)x, hw, part, nullptr, channels,
+                       nullptr);
   hipLaunchKernelGGL(k_channel_mean, dim3((channels + 63) / 64), dim3(64), 0, s, part, split, channels, hw, bias, mean);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
@@ -447,11 +450,11 @@ extern "C" int di_se_scale_add(di_dtype dt, const void* x, const float* scale, c
   const dim3 grid(ho_split(channels, hw, vec), channels);
   hipStream_t s = (hipStream_t)stream;
   if (dt == DI_BF16)
-    hipLaunchKernelGGL(k_se_scale_add<u16>, grid, dim3(HO_THREADS), 0, s, (const u16*)x, scale, bias,
-                       (const u16*)res, hw, (u16*)y);
+    hipLaunchKernelGGL((k_se_scale_add<u16, false>), grid, dim3(HO_THREADS), 0, s, (const u16*)x, scale, bias,
+                       (const u16*)res, hw, (u16*)y, channels, nullptr);
   else
-    hipLaunchKernelGGL(k_se_scale_add<float>, grid, dim3(HO_THREADS), 0, s, (const float*)x, scale, bias,
-                       (const float*)res, hw, (float*)y);
+    hipLaunchKernelGGL((k_se_scale_add<float, false>), grid, dim3(HO_THREADS), 0, s, (const float*)x, scale, bias,
+                       (const float*)res, hw, (float*)y, channels, nullptr);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
 }
@@ -464,9 +467,11 @@ extern "C" int di_plane_stats(di_dtype dt, const void* x, int32_t channels, int6
   int64_t* hdr = reinterpret_cast<int64_t*>(stats);
   double* part = reinterpret_cast<double*>(stats) + 2;
   if (dt == DI_BF16)
-    hipLaunchKernelGGL(k_inorm_stats<u16>, grid, dim3(HO_THREADS), 0, s, (const u16*)x, hw, part, hdr);
+    hipLaunchKernelGGL((k_inorm_stats<u16, false>), grid, dim3(HO_THREADS), 0, s, (const u16*)x, hw, part, hdr, channels,
+                       nullptr);
   else
-    hipLaunchKernelGGL(k_inorm_stats<float>, grid, dim3(HO_THREADS), 0, s, (const float*)x, hw, part, hdr);
+    hipLaunchKernelGGL((k_inorm_stats<float, false>), grid, dim3(HO_THREADS), 0, s, (const float*)x, hw, part, hdr, channels,
+                       nullptr);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
 }
@@ -476,8 +481,8 @@ extern "C" int di_head_norm_fold(const void* stats, int32_t channels, int64_t hw
                                  float* mean, void* stream) {
   if (!stats || ((uintptr_t)stats & 7) != 0 || channels <= 0 || channels > 65535 || hw <= 0) return DI_EINVAL;
   if (!(eps >= 0.f)) return DI_EINVAL;
-  hipLaunchKernelGGL(k_head_norm_fold, dim3(channels), dim3(HO_THREADS), 0, (hipStream_t)stream,
-                     (const double*)stats, hw, gamma, beta, eps, bias, scale, shift, mean);
+  hipLaunchKernelGGL(k_head_norm_fold<false>, dim3(channels), dim3(HO_THREADS), 0, (hipStream_t)stream,
+                     (const double*)stats, hw, gamma, beta, eps, bias, scale, shift, mean, channels, nullptr);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
 }
@@ -499,8 +504,8 @@ extern "C" int di_plane_stats_batch(di_dtype dt, const void* x, int32_t channels
   const int rc = hb_check_items(items, items_dev, count);
   if (rc != DI_OK) return rc;
   const dim3 grid(ho_max_split(items, count, channels), channels, count);
-  hipLaunchKernelGGL(k_plane_stats_batch, grid, dim3(HO_THREADS), 0, (hipStream_t)stream, (const u16*)x, channels,
-                     items_dev, (char*)stats);
+  hipLaunchKernelGGL((k_inorm_stats<u16, true>), grid, dim3(HO_THREADS), 0, (hipStream_t)stream, (const u16*)x, (int64_t)0,
+                     nullptr, (int64_t*)stats, channels, items_dev);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
 }
@@ -513,8 +518,8 @@ extern "C" int di_head_norm_fold_batch(const void* stats, int32_t channels, cons
   if (!(eps >= 0.f)) return DI_EINVAL;
   const int rc = hb_check_items(items, items_dev, count);
   if (rc != DI_OK) return rc;
-  hipLaunchKernelGGL(k_head_norm_fold_batch, dim3(channels, count), dim3(HO_THREADS), 0, (hipStream_t)stream,
-                     (const char*)stats, channels, items_dev, gamma, beta, eps, bias, scale, shift, mean);
+  hipLaunchKernelGGL(k_head_norm_fold<true>, dim3(channels, count), dim3(HO_THREADS), 0, (hipStream_t)stream,
+                     (const double*)stats, (int64_t)0, gamma, beta, eps, bias, scale, shift, mean, channels, items_dev);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
 }
@@ -527,8 +532,8 @@ extern "C" int di_se_scale_add_batch(di_dtype dt, const void* x, const float* sc
   const int rc = hb_check_items(items, items_dev, count);
   if (rc != DI_OK) return rc;
   const dim3 grid(ho_max_split(items, count, channels), channels, count);
-  hipLaunchKernelGGL(k_se_scale_add_batch, grid, dim3(HO_THREADS), 0, (hipStream_t)stream, (const u16*)x, scale, bias,
-                     (const u16*)res, channels, items_dev, (u16*)y);
+  hipLaunchKernelGGL((k_se_scale_add<u16, true>), grid, dim3(HO_THREADS), 0, (hipStream_t)stream, (const u16*)x, scale, bias,
+                     (const u16*)res, (int64_t)0, (u16*)y, channels, items_dev);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
 }

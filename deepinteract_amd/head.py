@@ -13,6 +13,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .engine import _ptr, _stream
+
 
 class HeadNormOps:
     """The head's HBM-bound passes on HIP (csrc/head_ops.hip): ELU(InstanceNorm2d(x))
@@ -58,9 +60,6 @@ class HeadNormOps:
         if x.dim() != 4 or x.shape[0] != 1 or not x.is_contiguous() or not x.is_cuda:
             raise ValueError("head ops take one contiguous NCHW [1, C, H, W] GPU image")
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def inorm_elu(self, x, norm: nn.InstanceNorm2d, out=None):
         """F.elu(norm(x)); out may be x (in place)."""
         self._check(x)
@@ -68,10 +67,8 @@ class HeadNormOps:
         y = torch.empty_like(x) if out is None else out
         w = self.work(C, hw, x.device)
         g, b = self.f32(norm.weight), self.f32(norm.bias)
-        self._lib.check(self.lib.di_inorm_elu(self._dt(x), ctypes.c_void_p(x.data_ptr()), C, hw,
-                                              ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(b.data_ptr()),
-                                              ctypes.c_float(norm.eps), ctypes.c_void_p(w.data_ptr()),
-                                              ctypes.c_void_p(y.data_ptr()), self._stream()), "di_inorm_elu")
+        self._lib.check(self.lib.di_inorm_elu(self._dt(x), _ptr(x), C, hw, _ptr(g), _ptr(b), ctypes.c_float(norm.eps),
+                                              _ptr(w), _ptr(y), _stream()), "di_inorm_elu")
         return y
 
     def channel_mean(self, x, bias=None):
@@ -81,10 +78,8 @@ class HeadNormOps:
         w = self.work(C, hw, x.device)
         m = torch.empty(1, C, dtype=torch.float32, device=x.device)
         b = self.f32(bias)
-        self._lib.check(self.lib.di_channel_mean(self._dt(x), ctypes.c_void_p(x.data_ptr()), C, hw,
-                                                 ctypes.c_void_p(0 if b is None else b.data_ptr()),
-                                                 ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(m.data_ptr()),
-                                                 self._stream()), "di_channel_mean")
+        self._lib.check(self.lib.di_channel_mean(self._dt(x), _ptr(x), C, hw, _ptr(b), _ptr(w), _ptr(m), _stream()),
+                        "di_channel_mean")
         return m
 
     def se_scale_add(self, x, scale, res, out=None, bias=None):
@@ -95,12 +90,8 @@ class HeadNormOps:
         s = scale.detach().reshape(-1).float().contiguous()
         b = self.f32(bias)
         y = torch.empty_like(x) if out is None else out
-        self._lib.check(self.lib.di_se_scale_add(self._dt(x), ctypes.c_void_p(x.data_ptr()),
-                                                 ctypes.c_void_p(s.data_ptr()),
-                                                 ctypes.c_void_p(0 if b is None else b.data_ptr()),
-                                                 ctypes.c_void_p(res.data_ptr()), C, hw,
-                                                 ctypes.c_void_p(y.data_ptr()), self._stream()),
-                        "di_se_scale_add")
+        self._lib.check(self.lib.di_se_scale_add(self._dt(x), _ptr(x), _ptr(s), _ptr(b), _ptr(res), C, hw, _ptr(y),
+                                                 _stream()), "di_se_scale_add")
         return y
 
 
@@ -113,11 +104,8 @@ class HeadNormOps:
             raise ValueError("the batch's gates are contiguous fp32 [count, C] rows")
         b = self.f32(bias)
         y = torch.empty_like(x) if out is None else out
-        self._lib.check(self.lib.di_se_scale_add_batch(self._lib.DI_BF16, ctypes.c_void_p(x.data_ptr()),
-                                                       ctypes.c_void_p(scale.data_ptr()),
-                                                       ctypes.c_void_p(0 if b is None else b.data_ptr()),
-                                                       ctypes.c_void_p(res.data_ptr()), C, hb.items, hb.items_ptr,
-                                                       hb.count, ctypes.c_void_p(y.data_ptr()), self._stream()),
+        self._lib.check(self.lib.di_se_scale_add_batch(self._lib.DI_BF16, _ptr(x), _ptr(scale), _ptr(b), _ptr(res), C,
+                                                       hb.items, hb.items_ptr, hb.count, _ptr(y), _stream()),
                         "di_se_scale_add_batch")
         return y
 
@@ -133,9 +121,8 @@ class HeadNormOps:
         if tuple(w1.shape) != (hidden, C) or tuple(w2.shape) != (C, hidden):
             raise ValueError(f"the SE block takes {w1.shape[1]} channels, the means have {C}")
         g = torch.empty_like(mean) if out is None else out
-        self._lib.check(self.lib.di_se_gate(*(ctypes.c_void_p(t.data_ptr()) for t in (mean, w1, b1, w2, b2)),
-                                            count, C, hidden, ctypes.c_void_p(g.data_ptr()), self._stream()),
-                        "di_se_gate")
+        self._lib.check(self.lib.di_se_gate(*(_ptr(t) for t in (mean, w1, b1, w2, b2)), count, C, hidden, _ptr(g),
+                                            _stream()), "di_se_gate")
         return g
 
 
@@ -174,7 +161,7 @@ class HeadBatch:
         self.px_off = [it.px_off for it in self.items]
         self.stats_off = [it.stats_off for it in self.items]
         self.items_dev = _table_to_device(self.items, self.device)
-        self.items_ptr = ctypes.c_void_p(self.items_dev.data_ptr())
+        self.items_ptr = _ptr(self.items_dev)
         C = self.CHANNELS
         bf = dict(dtype=torch.bfloat16, device=self.device)
         self.wide = [torch.empty(C * self.pixels, **bf) for _ in range(2)]
@@ -231,12 +218,14 @@ class HeadConvOps:
         if x.dim() != 4 or x.shape[0] != 1 or not x.is_contiguous() or not x.is_cuda or x.dtype != torch.bfloat16:
             raise ValueError("head convolutions take one contiguous NCHW [1, C, H, W] bf16 GPU image")
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     @staticmethod
-    def _ptr(t):
-        return ctypes.c_void_p(0 if t is None else t.data_ptr())
+    def _check_params(weight=None, vectors=()):
+        """The checks conv and conv_batch share: the weight tensor (if given) and fp32 per-channel vectors."""
+        if weight is not None and (weight.dtype != torch.bfloat16 or not weight.is_contiguous() or weight.dim() != 4):
+            raise ValueError("head conv weights are the module's contiguous bf16 [Cout, Cin, k, k] tensor")
+        for v in vectors:
+            if v is not None and (v.dtype != torch.float32 or not v.is_contiguous()):
+                raise ValueError("per-channel vectors are contiguous fp32")
 
     def stats_buffer(self, C, H, W, device):
         """The statistics buffer the next conv / plane_stats writes and the next fold reads (one,
@@ -252,21 +241,17 @@ class HeadConvOps:
         [Cout, Cin, k, k] bf16 tensor; bias, in_scale, in_shift: fp32 per-channel vectors or None.
         Returns y, or (y, stats buffer) with stats=True."""
         self._check(x)
-        if weight.dtype != torch.bfloat16 or not weight.is_contiguous() or weight.dim() != 4:
-            raise ValueError("head conv weights are the module's contiguous bf16 [Cout, Cin, k, k] tensor")
-        for v in (bias, in_scale, in_shift):
-            if v is not None and (v.dtype != torch.float32 or not v.is_contiguous()):
-                raise ValueError("per-channel vectors are contiguous fp32")
+        self._check_params(weight, (bias, in_scale, in_shift))
         _, C, H, W = x.shape
         cout, cin, k, _ = weight.shape
         if cin != C:
             raise ValueError(f"weight takes {cin} channels, the image has {C}")
         y = torch.empty(1, cout, H, W, dtype=x.dtype, device=x.device)
         st = self.stats_buffer(cout, H, W, x.device) if stats else None
-        args = self._lib.DiHeadConvArgs(x.data_ptr(), weight.data_ptr(), self._ptr(in_scale).value,
-                                        self._ptr(in_shift).value, self._ptr(bias).value, y.data_ptr(),
-                                        self._ptr(st).value, C, cout, H, W, k, int(dilation), int(bool(in_elu)))
-        self._lib.check(self.lib.di_head_conv(self._lib.DI_BF16, ctypes.byref(args), self._stream()), "di_head_conv")
+        args = self._lib.DiHeadConvArgs(x.data_ptr(), weight.data_ptr(), _ptr(in_scale).value,
+                                        _ptr(in_shift).value, _ptr(bias).value, y.data_ptr(),
+                                        _ptr(st).value, C, cout, H, W, k, int(dilation), int(bool(in_elu)))
+        self._lib.check(self.lib.di_head_conv(self._lib.DI_BF16, ctypes.byref(args), _stream()), "di_head_conv")
         return (y, st) if stats else y
 
     def plane_stats(self, x):
@@ -274,18 +259,18 @@ class HeadConvOps:
         self._check(x)
         _, C, H, W = x.shape
         st = self.stats_buffer(C, H, W, x.device)
-        self._lib.check(self.lib.di_plane_stats(self._lib.DI_BF16, self._ptr(x), C, H * W, self._ptr(st),
-                                                self._stream()), "di_plane_stats")
+        self._lib.check(self.lib.di_plane_stats(self._lib.DI_BF16, _ptr(x), C, H * W, _ptr(st),
+                                                _stream()), "di_plane_stats")
         return st
 
     def fold(self, st, C, hw, gamma=None, beta=None, eps=0.0, bias=None, want=("scale", "shift")):
         """Fold a statistics buffer into fp32 [C] vectors: scale = gamma / sqrt(var + eps),
         shift = beta - mean * scale, mean = mean (+ bias). Returns the ones named in ``want``, in order."""
         out = {k: torch.empty(C, dtype=torch.float32, device=st.device) for k in want}
-        self._lib.check(self.lib.di_head_norm_fold(self._ptr(st), C, hw, self._ptr(gamma), self._ptr(beta),
-                                                   ctypes.c_float(eps), self._ptr(bias), self._ptr(out.get("scale")),
-                                                   self._ptr(out.get("shift")), self._ptr(out.get("mean")),
-                                                   self._stream()), "di_head_norm_fold")
+        self._lib.check(self.lib.di_head_norm_fold(_ptr(st), C, hw, _ptr(gamma), _ptr(beta),
+                                                   ctypes.c_float(eps), _ptr(bias), _ptr(out.get("scale")),
+                                                   _ptr(out.get("shift")), _ptr(out.get("mean")),
+                                                   _stream()), "di_head_norm_fold")
         return tuple(out[k] for k in want)
 
 
@@ -296,32 +281,30 @@ class HeadConvOps:
         (None: a new buffer), in_scale / in_shift [count, Cin] fp32 rows or None, weight / bias shared.
         With stats=True the batch's statistics buffer is written (every item at its stats_off).
         Returns y, or (y, hb.stats)."""
-        if weight.dtype != torch.bfloat16 or not weight.is_contiguous() or weight.dim() != 4:
-            raise ValueError("head conv weights are the module's contiguous bf16 [Cout, Cin, k, k] tensor")
+        self._check_params(weight)
         cout, cin, k, _ = weight.shape
         hb.check_packed(x, cin)
         for v in (in_scale, in_shift):
             if v is not None and (v.dtype != torch.float32 or not v.is_contiguous()
                                   or tuple(v.shape) != (hb.count, cin)):
                 raise ValueError("the batch's scale / shift are contiguous fp32 [count, Cin] rows")
-        if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
-            raise ValueError("per-channel vectors are contiguous fp32")
+        self._check_params(vectors=(bias,))
         if y is None:
             y = torch.empty(cout * hb.pixels, dtype=torch.bfloat16, device=x.device)
         hb.check_packed(y, cout)
-        args = self._lib.DiHeadConvArgs(x.data_ptr(), weight.data_ptr(), self._ptr(in_scale).value,
-                                        self._ptr(in_shift).value, self._ptr(bias).value, y.data_ptr(),
+        args = self._lib.DiHeadConvArgs(x.data_ptr(), weight.data_ptr(), _ptr(in_scale).value,
+                                        _ptr(in_shift).value, _ptr(bias).value, y.data_ptr(),
                                         hb.stats.data_ptr() if stats else None, cin, cout, 0, 0, k, int(dilation),
                                         int(bool(in_elu)))
         self._lib.check(self.lib.di_head_conv_batch(self._lib.DI_BF16, ctypes.byref(args), hb.items, hb.items_ptr,
-                                                    hb.count, self._stream()), "di_head_conv_batch")
+                                                    hb.count, _stream()), "di_head_conv_batch")
         return (y, hb.stats) if stats else y
 
     def plane_stats_batch(self, hb, x, C):
         """The batch's statistics buffer of a packed C-channel buffer (one read pass)."""
         hb.check_packed(x, C)
-        self._lib.check(self.lib.di_plane_stats_batch(self._lib.DI_BF16, self._ptr(x), C, hb.items, hb.items_ptr,
-                                                      hb.count, self._ptr(hb.stats), self._stream()),
+        self._lib.check(self.lib.di_plane_stats_batch(self._lib.DI_BF16, _ptr(x), C, hb.items, hb.items_ptr,
+                                                      hb.count, _ptr(hb.stats), _stream()),
                         "di_plane_stats_batch")
         return hb.stats
 
@@ -330,11 +313,11 @@ class HeadConvOps:
         preallocated rows by name (None: new tensors)."""
         out = {k: (out[k] if out is not None else torch.empty(hb.count, C, dtype=torch.float32, device=st.device))
                for k in want}
-        self._lib.check(self.lib.di_head_norm_fold_batch(self._ptr(st), C, hb.items, hb.items_ptr, hb.count,
-                                                         self._ptr(gamma), self._ptr(beta), ctypes.c_float(eps),
-                                                         self._ptr(bias), self._ptr(out.get("scale")),
-                                                         self._ptr(out.get("shift")), self._ptr(out.get("mean")),
-                                                         self._stream()), "di_head_norm_fold_batch")
+        self._lib.check(self.lib.di_head_norm_fold_batch(_ptr(st), C, hb.items, hb.items_ptr, hb.count,
+                                                         _ptr(gamma), _ptr(beta), ctypes.c_float(eps),
+                                                         _ptr(bias), _ptr(out.get("scale")),
+                                                         _ptr(out.get("shift")), _ptr(out.get("mean")),
+                                                         _stream()), "di_head_norm_fold_batch")
         return tuple(out[k] for k in want)
 
 

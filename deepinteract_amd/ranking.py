@@ -109,9 +109,7 @@ class ContactRankOp:
         if nb < 0:
             raise ValueError(f"contact ranking of {n} elements, k = {k}: code {nb} "
                              f"(1 <= k <= min(n, {_lib.DI_RANK_MAX_K}), n < 2^29)")
-        if self._work is None or self._work.numel() * 8 < nb:
-            self._work = torch.empty((nb + 7) // 8, dtype=torch.int64, device=self.device)
-        return self._work
+        return _grow(self, nb)
 
     def _check(self, logits, k, labels):
         """The argument checks of one complex: (dtype code, l1, l2, k)."""
@@ -312,9 +310,7 @@ class ContactAucOp:
         if nb < 0:
             raise ValueError(f"contact AUC of {n} elements, max_pos = {max_pos}: code {nb} "
                              "(1 <= max_pos <= n < 2^29)")
-        if self._work is None or self._work.numel() * 8 < nb:
-            self._work = torch.empty((nb + 7) // 8, dtype=torch.int64, device=self.device)
-        return self._work
+        return _grow(self, nb)
 
     def _run(self, probs, labels, max_pos):
         n = probs.numel()
@@ -395,32 +391,12 @@ def labels_from_examples(examples, l1: int, l2: int):
     """The reference's ``examples`` [n, 3] = (i, j, label) rows of one complex as a uint8 [l1 * l2]
     label map on the device of ``examples``. Raises ValueError unless the rows cover every pair
     exactly once with indices in range and labels in {0, 1}."""
-    if examples.dim() != 2 or examples.shape[1] != 3:
-        raise ValueError("examples: [n, 3] rows of (i, j, label)")
-    n = l1 * l2
-    if examples.shape[0] != n:
-        raise ValueError(f"examples: {examples.shape[0]} rows for {l1} x {l2} = {n} pairs "
-                         "(every pair exactly once)")
-    ex = examples.to(torch.int64)
-    i, j, lab = ex[:, 0], ex[:, 1], ex[:, 2]
-    if bool(((i < 0) | (i >= l1) | (j < 0) | (j >= l2)).any()):
-        raise ValueError("examples: a pair index outside the complex")
-    if bool(((lab != 0) & (lab != 1)).any()):
-        raise ValueError("examples: labels must be 0 or 1")
-    flat = i * l2 + j
-    seen = torch.zeros(n, dtype=torch.int32, device=examples.device)
-    seen.index_add_(0, flat, torch.ones(n, dtype=torch.int32, device=examples.device))
-    if bool((seen != 1).any()):
-        raise ValueError("examples: a pair is missing or listed twice")
-    out = torch.zeros(n, dtype=torch.uint8, device=examples.device)
-    out[flat] = lab.to(torch.uint8)
-    return out
+    return labels_from_examples_batch([examples], [(l1, l2)])[0]
 
 
 def labels_from_examples_batch(examples_list, shapes):
     """``labels_from_examples`` for many complexes: shapes[i] = (l1, l2) of examples_list[i]. The same
-    validation and the same result per complex, with ONE host read for the whole batch (the single
-    function reads the device three times per complex)."""
+    validation and the same result per complex, with ONE host read for the whole batch."""
     if len(examples_list) != len(shapes):
         raise ValueError("examples: one (l1, l2) per complex")
     flags, outs = [], []

@@ -94,6 +94,45 @@ def test_channel_mean(ops, shape, dtype):
     assert float((m.double() - ref).abs().max()) < 1e-6 * float(ref.abs().max()) + 1e-7
 
 
+def _ho_split(C, hw, vec):
+    """csrc/head_ops.hip's ho_split: the slices per channel plane = the statistics header's count."""
+    split = min(max((2048 + C - 1) // C, 1), 64)
+    while split > 1 and (hw // vec) // split < 2 * 256:
+        split >>= 1
+    return split
+
+
+# (3, 5, 7): planes of 35 elements, none 16-B aligned after the first: whole vectors with scalar heads
+# and tails; (8, 33, 70): the same at 2310 elements; (5, 1, 3): planes shorter than one fp32 vector, all
+# scalar
+@pytest.mark.parametrize("shape", [(3, 5, 7), (8, 33, 70), (5, 1, 3)])
+def test_plane_stats_and_fold_f32(shape):
+    """di_plane_stats + di_head_norm_fold on an fp32 image (k_inorm_stats<float> with a header) against
+    an fp64 evaluation, at test_gpu_head_conv.test_plane_stats_and_fold's bound."""
+    from deepinteract_amd import _lib
+    from deepinteract_amd.engine import _ptr, _stream
+    from deepinteract_amd.head import HeadConvOps
+    cops = HeadConvOps("cuda")
+    C, H, W = shape
+    x = _x(C, H, W, 11)
+    g = torch.Generator().manual_seed(12)
+    gamma, beta, bias = ((1 + 0.3 * torch.randn(C, generator=g)).cuda(), (0.3 * torch.randn(C, generator=g)).cuda(),
+                         torch.randn(C, generator=g).cuda())
+    st = cops.stats_buffer(C, H, W, x.device)
+    st.fill_(float("nan"))
+    _lib.check(cops.lib.di_plane_stats(_lib.DI_F32, _ptr(x), C, H * W, _ptr(st), _stream()), "di_plane_stats")
+    assert st[:2].view(torch.int64).tolist() == [_ho_split(C, H * W, 4), 0]
+    sc, sh, mean = cops.fold(st, C, H * W, gamma, beta, 1e-6, bias, want=("scale", "shift", "mean"))
+    xd = x.double()
+    m = xd.mean(dim=(0, 2, 3))
+    var = (xd * xd).mean(dim=(0, 2, 3)) - m * m
+    rsc = gamma.double() / torch.sqrt(var + 1e-6)
+    for got, ref in ((sc, rsc), (sh, beta.double() - m * rsc), (mean, m + bias.double())):
+        err, bound = float((got.double() - ref).abs().max()), 1e-6 * float(ref.abs().max()) + 1e-7
+        print(f"{shape}: err {err:.3e} bound {bound:.3e}")
+        assert err < bound
+
+
 def test_head_body_with_hip_ops_matches_torch_f32():
     """The whole head (58 ResNet blocks) with the HIP passes (bias folding, SE fusion) vs torch's
     passes, fp32, 64x64."""
