@@ -141,11 +141,16 @@ class OverlappedSchedule:
     streams that turn out not to run concurrently put the schedule in "ordered" mode (module doc).
     tap(job, h, e): called right after each micro-batch's forward is issued, with the engine's node /
     edge feature outputs of that forward, while the GeoT stream is current (stream-ordered copies taken
-    there see exactly what the schedule computed, before the workspace is reused)."""
+    there see exactly what the schedule computed, before the workspace is reused).
+    allow_gave_up: what the check at a queue rollover (every `capacity_steps` steps) does when stream
+    waves gave up waiting for a signal during the epoch. False (default): raise, as check() does -- the
+    overlap the schedule exists for did not happen. True: go on -- the help launches completed every
+    job, so the outputs are exact, and the count starts again from zero with the new epoch (read it
+    with check(allow_gave_up=True) before the rollover if it matters). An error bit raises either way."""
 
     def __init__(self, eng, mbs, h1r, h2r, l1, l2, sinks, s_geot=None, s_pair=None, ring=16, help_every=4,
                  stream_blocks=0, stream_waves=0, help_blocks=0, help_waves=0, patience_ms=20.0,
-                 capacity_steps=64, jobs_per_launch=0, discard_outputs=False, tap=None):
+                 capacity_steps=64, jobs_per_launch=0, discard_outputs=False, tap=None, allow_gave_up=False):
         if help_every < 1 or ring < 2 * help_every:
             raise ValueError("need ring >= 2 * help_every")
         if eng.dtype == "bf16" and not eng.fuse_embed_init and eng.resident_init:
@@ -160,6 +165,7 @@ class OverlappedSchedule:
             s_geot, s_pair = s_geot or g, s_pair or p
         self.s_geot, self.s_pair = s_geot, s_pair
         self.tap, self.discard_outputs = tap, bool(discard_outputs)
+        self.allow_gave_up = bool(allow_gave_up)
         # the property the persistent pair launch needs (module doc); measured, not assumed
         self.concurrent = s_geot is not s_pair and streams_concurrent(s_pair, s_geot)
         self.mode = "overlapped" if self.concurrent else "ordered"
@@ -221,12 +227,14 @@ class OverlappedSchedule:
                                                ctypes.byref(self.stream_launch), self.patience, st), "di_pair_stream")
 
     def _rollover(self):
-        """Restart job numbering when the queue's counters are used up (drain, sync, zero)."""
+        """Restart job numbering when the queue's counters are used up (drain, sync, check, zero). The
+        error word always raises here; stream waves that gave up raise unless the schedule was built
+        with allow_gave_up (the epoch's outputs are complete either way)."""
         if self.next_job + len(self.mbs) <= self.queue.capacity:
             return
         self.finish()
         torch.cuda.synchronize(self.eng.device)
-        self.check()
+        self.check(allow_gave_up=self.allow_gave_up)
         self.queue.reset()
         self.next_job = self.helped = 0
         self.pending = -1
@@ -284,15 +292,16 @@ class OverlappedSchedule:
                 _lib.check(self.eng.lib.di_pair_signal(self._q(), self.pending, st), "di_pair_signal")
                 self.pending = -1
 
-    def check(self, allow_gave_up=False):
+    def check(self, allow_gave_up=None):
         """Host read of the queue's counters (synchronises). Raises if a help launch's completion wait
         timed out or a stream wave read a non-increasing ticket (error word), and -- unless
-        allow_gave_up -- if any stream wave gave up waiting for a signal: the outputs are still complete
-        then (the help launches wrote them), but the overlap the schedule exists for did not happen."""
+        allow_gave_up (None: the constructor's setting, False by default) -- if any stream wave gave up
+        waiting for a signal: the outputs are still complete then (the help launches wrote them), but
+        the overlap the schedule exists for did not happen."""
         c = self.queue.counters()
         if c["error"]:
             raise RuntimeError(f"pair queue error {c}")
-        if c["gave_up"] and not allow_gave_up:
+        if c["gave_up"] and not (self.allow_gave_up if allow_gave_up is None else allow_gave_up):
             raise RuntimeError(f"pair stream waves gave up waiting for their signal (the streams did not run "
                                f"concurrently): {c}")
         return c
