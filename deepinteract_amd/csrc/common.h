@@ -56,7 +56,6 @@ typedef uint16_t u16;
 
 constexpr int HID = 128;          // num_gnn_hidden_channels
 constexpr int NFEAT_E = 28;       // edge feature columns (FEATURE_INDICES)
-constexpr int NFEAT_N = 113;      // node feature columns
 constexpr int BLK = 512;          // elements per packed (16 out x 32 in) weight block
 constexpr int MAT128 = 32;        // blocks of a 128x128 matrix
 constexpr int ROWS_PER_WAVE = 16;
@@ -96,13 +95,6 @@ __device__ __forceinline__ void st4(u16* p, floatx4 v) {
   u.x = pack_bf16x2(v[0], v[1]);
   u.y = pack_bf16x2(v[2], v[3]);
   *reinterpret_cast<uint2*>(p) = u;
-}
-// non-temporal forms (write-once edge rows that do not fit in L2: kept from evicting weight stages)
-__device__ __forceinline__ void st4_nt(float* p, floatx4 v) { __builtin_nontemporal_store(v, reinterpret_cast<floatx4*>(p)); }
-__device__ __forceinline__ void st4_nt(u16* p, floatx4 v) {
-  typedef unsigned int uintx2 __attribute__((ext_vector_type(2)));
-  const uintx2 u = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
-  __builtin_nontemporal_store(u, reinterpret_cast<uintx2*>(p));
 }
 
 template <bool FAST>
@@ -264,15 +256,6 @@ __device__ __forceinline__ void silu2_(Act<NB>& a) {
     for (int r = 0; r < 4; ++r) a.v[b][r] = silu2<FAST>(a.v[b][r]);
 }
 
-// Pin an activation: an empty asm that reads and rewrites its registers, so every value is
-// computed HERE. Without it the compiler may sink a chain of VALU work (a gate product, a running
-// sum's terms) past later stages to its last use, keeping all the chain's inputs live meanwhile.
-template <int NB>
-__device__ __forceinline__ void pin(Act<NB>& a) {
-#pragma unroll
-  for (int b = 0; b < NB; ++b) asm volatile("" : "+v"(a.v[b]));
-}
-
 // a += k * b (one v_fma per value: folds the ln(2) of a log2-unit SiLU output into a residual add)
 template <int NB>
 __device__ __forceinline__ void add_scaled_(Act<NB>& a, const Act<NB>& b_, float k) {
@@ -313,11 +296,6 @@ struct Op<F32T, NS> {
   floatx4 f[2 * NS];
 };
 
-template <int NS>
-__device__ __forceinline__ void pin(Op<BF16T, NS>& o) {
-#pragma unroll
-  for (int s = 0; s < NS; ++s) asm volatile("" : "+v"(o.f[s]));
-}
 template <int NS>
 __device__ __forceinline__ void make_op(Op<BF16T, NS>& o, const Act<2 * NS>& a) {
 #pragma unroll
@@ -473,7 +451,7 @@ __device__ __forceinline__ void dma_vec(float* lds, const float* g, int n512) {
 //   makes it the current slot (w(), v()).
 // With DBUF the DMA of layer i+1 runs under layer i's MFMAs; the slot it overwrites was last read
 // in layer i-1, before the barrier inside next(). Call pattern per layer:
-//     pipe.next(); pipe.issue(next layer); compute(pipe.w(), pipe.v());
+//     w = pipe.next(); pipe.issue(next layer); compute(w, pipe.v());
 // The DMA pieces of a stage are split over the NW waves by wave index: a block launched with a
 // different wave count than NW would leave pieces unwritten (fewer waves) -- the kernels take NW
 // and their launch shape from one geometry struct (KernelGeo below), never from two constants.
@@ -533,7 +511,6 @@ struct WPipe {
     }
     return slot_w(cur);
   }
-  __device__ __forceinline__ const T* w() const { return slot_w(cur); }
   __device__ __forceinline__ const float* v() const { return slot_v(cur); }
 };
 
@@ -547,15 +524,6 @@ struct KernelGeo {
   static constexpr int THREADS = 64 * NW_;
   static constexpr int ROWS = ROWS_PER_WAVE * NW_;
 };
-
-// Single synchronous stage (kept for simple kernels).
-template <typename T>
-__device__ __forceinline__ void stage(T* lds, const T* g, int nblk) {
-  __syncthreads();
-  dma_blocks<WAVES>(lds, g, nblk);
-  lds_dma_wait();
-  __syncthreads();
-}
 
 // sum of the 32 features of head h (= blocks 2h, 2h+1) for this lane's row
 template <int NB>

@@ -115,18 +115,15 @@ __device__ __forceinline__ int row_id() {
   return blockIdx.x * (NW * ROWS_PER_WAVE) + (threadIdx.x >> 6) * ROWS_PER_WAVE + (threadIdx.x & 15);
 }
 
-// Launch geometry per storage dtype. bf16 (the benchmark path): 4-wave blocks, two per CU
-// (2 x 80 KiB of LDS, <=256 VGPRs), each double-buffering its weight stages so the LDS-DMA of
-// layer i+1 runs under layer i's MFMAs. Two independent blocks per CU matter: the waves of ONE
-// block meet at every stage barrier in lockstep, so only waves of the other block can fill a
-// SIMD's MFMA pipe while these run their SiLU VALU work (and vice versa). Measured alternatives
-// (round 1-2): one 8-wave block per CU with or without a decoupled ring, persistent
-// tiles, XCD-aware tile order, static wave priority, pumped DMA pieces -- all slower.
-// fp32 (parity path; stages twice as large): same geometry, synchronous single-buffered stages.
+// Launch geometry of k_edge_layer per storage dtype: 4-wave blocks, two per CU (<= 240 VGPRs each).
+// Two independent blocks per CU matter: the waves of ONE block meet at every stage barrier in
+// lockstep, so only waves of the other block can fill a SIMD's MFMA pipe while these run their SiLU
+// VALU work (and vice versa). bf16 (di_conformation) double-buffers its weight stages (2 x 36.5 KiB
+// per block) so the LDS-DMA of layer i+1 runs under layer i's MFMAs; fp32 (stages twice as large,
+// 72.5 KiB) stages synchronously through one slot.
 template <class DT>
 struct Geo : KernelGeo<4> {
   static constexpr bool DBUF = DT::kBF16;
-  static constexpr int CAP = 40;  // blocks per weight stage buffer
 };
 
 // The edge's own input row F: bf16 path keeps it in registers as a packed MFMA operand (its
@@ -136,11 +133,6 @@ struct FRow;
 template <>
 struct FRow<BF16T> {
   Op<BF16T, 4> op;
-  __device__ void load(const u16* row, int g) {
-    Act<8> a;
-    load_row(a, row, g);
-    make_op(op, a);
-  }
   // the raw row IS the packed operand: op.f[s] = {u[2s].x, u[2s].y, u[2s+1].x, u[2s+1].y}
   __device__ void set_raw(const RawRow<u16>& r) {
 #pragma unroll
@@ -153,7 +145,6 @@ struct FRow<BF16T> {
 template <>
 struct FRow<F32T> {
   Op<F32T, 4> tmp;
-  __device__ void load(const float*, int) {}
   __device__ void act(Act<8>& a, const float* row, int g) const { load_row(a, row, g); }
   __device__ const Op<F32T, 4>& operand(const float* row, int g) {
     Act<8> a;

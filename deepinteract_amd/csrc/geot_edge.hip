@@ -97,6 +97,7 @@ void k_edge_layer(EdgeArgs a) {
   using T = typename DT::T;
   using G = Geo<DT>;
   constexpr bool FAST = DT::kBF16;
+  static_assert(!DT::kBF16 || MODE == 2, "the bf16 layers are k_edge_x32_ring's; bf16 here is di_conformation only");
   __shared__ __attribute__((aligned(16))) char lds[(G::DBUF ? 2 : 1) * EdgePipe<DT>::SLOT_BYTES];
   const int lane = lane_id(), g = lane >> 4;
   const int r = row_id<G::NW>();
@@ -239,14 +240,14 @@ void k_edge_layer(EdgeArgs a) {
       for (int b = 0; b < 8; ++b)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          float sc = FAST ? (kq.v[b][q] * qd.v[b][q]) * (1.0f / scale) : (kq.v[b][q] * qd.v[b][q]) / scale;
+          float sc = (kq.v[b][q] * qd.v[b][q]) / scale;
           sc = fminf(fmaxf(sc, -5.f), 5.f);
           p.v[b][q] = sc * p.v[b][q];  // score = e_out
         }
     }
     floatx4 al;
 #pragma unroll
-    for (int h = 0; h < 4; ++h) al[h] = expf_<FAST>(fminf(fmaxf(head_sum(p, h), -5.f), 5.f));
+    for (int h = 0; h < 4; ++h) al[h] = expf(fminf(fmaxf(head_sum(p, h), -5.f), 5.f));
     if (valid && g == 0) st4(a.alpha_out + (int64_t)e * 4, al);
 
     if constexpr (!FINAL) {
@@ -268,7 +269,7 @@ void k_edge_layer(EdgeArgs a) {
         Act<8> t;
         init_vec_lds(t, st.v(), g);
         linear<DT, 8, 4>(t, e1, w, lane);
-        silu2_<8, FAST>(t);
+        silu_<8, false>(t);
         w = st.next();  // edge_feats_MLP.3, input half
         linear<DT, 8, 4>(o, t, w, lane);
       }
@@ -279,17 +280,19 @@ void k_edge_layer(EdgeArgs a) {
       Act<8> fn;
       init_vec_lds(fn, st.v(), g);
       linear<DT, 8, 4>(fn, e1, w, lane);
-      silu_<8, FAST>(fn);
+      silu_<8, false>(fn);
       if (valid) store_edge_row(fn, reinterpret_cast<T*>(a.fn_out) + (int64_t)e * HID, g);
     }
   }
 }
 
 // ================================================================ fused edge layer on 32x32x16 MFMA (bf16)
-// The stage sequence and arithmetic of k_edge_layer<BF16T, MODE, GC>, with each wave's 32 rows as ONE
-// 32x32 tile (csrc/mfma32.h): a 128x128 linear is 32 v_mfma_f32_32x32x16_bf16 per wave. Weight stages
-// weight stages on an 8-wave LDS ring (k_edge_x32_ring below); the weight blobs are packed in the 32x32
-// fragment order (packing.pack_matrix32, di_blob_layout() == 32).
+// The bf16 edge layers: k_edge_layer's stage sequence (EL_ORDER / EL_SIZE / EL_VEC) with the log2-unit
+// SiLUs, the reciprocal score scale and __expf of the bf16 product, each wave's 32 rows as ONE 32x32
+// tile (csrc/mfma32.h): a 128x128 linear is 32 v_mfma_f32_32x32x16_bf16 per wave. The weight stages
+// arrive on an 8-wave LDS ring (k_edge_x32_ring below); the weight blobs are packed in the 32x32
+// fragment order (packing.pack_matrix32, di_blob_layout() == 32). Pinned to the fp64 oracle by
+// tests/test_gpu_geot_edge_shapes.py.
 
 // x through one ResBlock: two silu2(W . + b) layers packed as the next operand, then x += ln2 * silu2(W . + b)
 template <class ST>
@@ -765,33 +768,17 @@ __device__ __forceinline__ void dma_piece(rsrc4 r, uint32_t lds, int voff, int s
       : "memory", "m0");
 }
 
-// What one ring stage loads: up to three runs of packed 512-element blocks (laid out back to back in
-// the slot) and an optional bias vector (128 floats, after the slot's blocks).
-struct RingPieces {
-  const u16* w;  // blob base
-  int off[3], n[3];
-  int np;
-  const float* v;  // bias vector or null
-};
-// the bf16 edge layer's stages (EL_ORDER / EL_SIZE / EL_VEC): one run each
+// The bf16 edge layer's stage sequence on the ring. One stage is one run of packed 512-element blocks
+// of the layer's blob (EL_ORDER / EL_SIZE: first block, block count) and an optional bias vector
+// (EL_VEC: 128 floats, after the slot's blocks); global stage gs is stage gs % NS of the layer.
+// GC: as EdgeStages, the sequence starts at orig_msg_linear, which then carries ELV_OM.
 template <int NS, bool GC>
-struct EdgeRingSrc {
-  const u16* W;
-  const float* V;
-  __device__ RingPieces operator()(int gs) const {
-    const int s = gs % NS;
-    const int si = GC ? s + 2 : s;
-    const int vo = (GC && s == 0) ? ELV_OM : EL_VEC[si];
-    return {W, {EL_ORDER[si], 0, 0}, {EL_SIZE[si], 0, 0}, 1, vo >= 0 ? V + vo : nullptr};
-  }
-};
-
-template <class SRC, int NW = RING_NW>
-struct RingStagesT {
+struct RingStages {
   char* base;          // RING_SLOTS x RingSlot::SLOT_BYTES
   uint32_t* full;      // [RING_SLOTS]: stage uses published (1 per use)
-  uint32_t* freec;     // [RING_SLOTS]: wave releases (NW per use)
-  SRC src;             // global stage -> its weight runs and bias
+  uint32_t* freec;     // [RING_SLOTS]: wave releases (RING_NW per use)
+  const u16* W;        // the layer's weight blob
+  const float* V;      // its bias vectors
   int wave;
   int total;           // global stages of this block
   int g = 0;           // next stage to consume
@@ -802,36 +789,37 @@ struct RingStagesT {
   __device__ float* slot_v(int sl) const {
     return reinterpret_cast<float*>(base + sl * RingSlot::SLOT_BYTES + EL_CAP * BLK * 2);
   }
-  // global stage gs is loaded and published by ONE wave, gs % NW (its owner): all its 1-KiB
+  // global stage gs is loaded and published by ONE wave, gs % RING_NW (its owner): all its 1-KiB
   // LDS-DMA pieces and the bias vector. Issued by inline asm: the compiler's waitcnt pass cannot tell a
   // ring slot (runtime index) from the one being read and would wait for every piece before the next
   // ds_read -- completion is what FULL tracks (the owner's vmcnt(0), then its publish).
   __device__ void issue_one(int gs) {
-    const RingPieces p = src(gs);
+    const int s = gs % NS;
+    const int si = GC ? s + 2 : s;
+    const int vo = (GC && s == 0) ? ELV_OM : EL_VEC[si];
+    const int off = EL_ORDER[si], n = EL_SIZE[si];  // the stage's run: first block, block count
+    const float* v = vo >= 0 ? V + vo : nullptr;    // its bias vector
     const int sl = gs % RING_SLOTS;
-    uint32_t dst = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)slot_w(sl);
+    const uint32_t dst = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)slot_w(sl);
     const int loff = (threadIdx.x & 63) * 16;
-    for (int k = 0; k < p.np; ++k) {
-      const rsrc4 r = rsrc_of(p.w + p.off[k] * BLK);
-      for (int i = 0; i < p.n[k]; ++i) dma_piece(r, dst + i * 1024, loff, i * 1024);  // 1 KiB per block
-      dst += p.n[k] * 1024;
-    }
-    if (p.v && (threadIdx.x & 63) < 32)
-      dma_piece(rsrc_of(p.v), (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)slot_v(sl), loff, 0);
+    const rsrc4 r = rsrc_of(W + off * BLK);
+    for (int i = 0; i < n; ++i) dma_piece(r, dst + i * 1024, loff, i * 1024);  // 1 KiB per block
+    if (v && (threadIdx.x & 63) < 32)
+      dma_piece(rsrc_of(v), (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)slot_v(sl), loff, 0);
     pending = gs;
   }
   // stages issued ahead of the one consumed, owners' slots permitting
   __device__ void issue_ahead() {
     for (; issued <= g + RING_AHEAD && issued < total; ++issued) {
-      if (issued % NW != wave) continue;
+      if (issued % RING_NW != wave) continue;
       const int prev = issued - RING_SLOTS;  // the stage that used this slot last
-      if (prev >= 0) lds_wait_ge(freec + issued % RING_SLOTS, (uint32_t)(NW * (prev / RING_SLOTS + 1)));
+      if (prev >= 0) lds_wait_ge(freec + issued % RING_SLOTS, (uint32_t)(RING_NW * (prev / RING_SLOTS + 1)));
       issue_one(issued);
     }
   }
   __device__ void fill() {
     for (; issued < RING_AHEAD && issued < total; ++issued)
-      if (issued % NW == wave) issue_one(issued);
+      if (issued % RING_NW == wave) issue_one(issued);
   }
   // settle(): an empty asm reading the rows the caller loaded just before this call (F rows, K / Q):
   // the compiler then waits for them HERE, after the vmcnt(0) that has landed them anyway -- not after
@@ -858,8 +846,6 @@ struct RingStagesT {
   }
   __device__ const float* v() const { return slot_v(cur); }
 };
-template <int NS, bool GC>
-using RingStages = RingStagesT<EdgeRingSrc<NS, GC>>;
 
 // Z0 (di_edge_layer_z): layer 0 on z0 rows; InitEdge's combined_linear_2 (8 packed blocks, 8 KiB of
 // the kind-1 blob at IE_C1 + 8) stays in LDS beside the ring for the block's lifetime
@@ -890,7 +876,7 @@ void k_edge_x32_ring(EdgeArgs a, int ntiles) {
     wc2 = wc2_lds;
   }
   __syncthreads();
-  RingStages<NS, GC> st{lds, counters, counters + RING_SLOTS, {reinterpret_cast<const u16*>(a.wmat), a.wvec}, wave,
+  RingStages<NS, GC> st{lds, counters, counters + RING_SLOTS, reinterpret_cast<const u16*>(a.wmat), a.wvec, wave,
                         my_tiles * NS};
   st.fill();
 #pragma unroll 1

@@ -53,22 +53,22 @@ __global__ __launch_bounds__(EmbedGeo::THREADS) void k_node_embed(EmbedArgs a) {
 // the orientation terms are the packed constants IEV_ORC / IEV_OGATE; the layer-0
 // silu(nbr_linear(F)) rows are only computed when fn_out is given (the grouped edge kernel does
 // not gather them for such batches).
-// Launch shape of the bf16 InitEdge: weights staged synchronously in one 40-KiB slot per block,
-// so three blocks share a CU (the kernel holds 150 VGPRs) and cover each other's stage waits.
-// Measured (C3 micro-batch, GEO_REF): alone 109 vs 118 us with two double-buffered blocks, beside
-// the pair stream 168 vs 187 us; four blocks (128 VGPRs) spill: 130 / 206 us.
-template <class DT>
-struct InitGeo : Geo<DT> {
-  static constexpr bool DBUF = false;
-  static constexpr int WPE = DT::kBF16 ? 3 : 2;  // blocks (waves per SIMD) per CU
+// Both InitEdge kernels (k_init_edge: fp32 on 16x16 MFMA, k_init_x32: bf16 on 32x32) stage their
+// weights synchronously through ONE slot of INIT_CAP blocks per block, so several blocks share a CU
+// and cover each other's stage waits (measured shapes: DESIGN.md §8).
+constexpr int INIT_CAP = 40;  // blocks of the weight-stage slot (the largest phase: a geometric term)
+// k_init_edge's launch geometry: 4-wave blocks of 64 edges, two per CU (an 80-KiB fp32 slot each)
+struct InitGeo : KernelGeo<4> {
+  static constexpr int WPE = 2;  // blocks (waves per SIMD) per CU
 };
 // The node embedding (+ layer-0 Q/K/V) as the first `embed_blocks` blocks of an InitEdge launch
-// (di_embed_init_edge): same stages and arithmetic as k_node_embed<BF16T> through InitEdge's single
+// (di_embed_init_edge): same stages and arithmetic as k_node_embed<DT> through InitEdge's single
 // 40-block LDS slot, so the two run side by side inside one launch instead of the embedding on a
-// side stream (whose blocks find no LDS beside InitEdge's until its tail).
+// side stream (whose blocks find no LDS beside InitEdge's until its tail). Instantiated for both
+// hosts: <F32T, InitGeo::NW> in k_init_edge, <BF16T, InitX32Geo::NW> in k_init_x32.
 // (NW: the launch's waves per block, 16 rows each)
-template <class DT, int NW = InitGeo<DT>::NW>
-__device__ __forceinline__ void embed_block(const EmbedArgs& ea, WPipe<typename DT::T, NW, false, InitGeo<DT>::CAP>& pipe,
+template <class DT, int NW>
+__device__ __forceinline__ void embed_block(const EmbedArgs& ea, WPipe<typename DT::T, NW, false, INIT_CAP>& pipe,
                                             int blk, int lane, int g) {
   using T = typename DT::T;
   const int r = blk * ROWS_PER_WAVE * NW + (threadIdx.x >> 6) * ROWS_PER_WAVE + (lane & 15);
@@ -113,34 +113,31 @@ __device__ __forceinline__ void embed_block(const EmbedArgs& ea, WPipe<typename 
   }
 }
 
-template <class DT, bool GC>
-__global__ __attribute__((amdgpu_flat_work_group_size(1, InitGeo<DT>::THREADS),
-                          amdgpu_waves_per_eu(InitGeo<DT>::WPE, InitGeo<DT>::WPE)))
+// The fp32 InitEdge (the reference's precision: plain SiLU, unscaled weights); bf16 is k_init_x32.
+template <bool GC>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, InitGeo::THREADS),
+                          amdgpu_waves_per_eu(InitGeo::WPE, InitGeo::WPE)))
 void k_init_edge(InitArgs a, EmbedArgs ea, int embed_blocks) {
   pq_signal_at_start(ea.sig_q, ea.sig_job);
-  using T = typename DT::T;
-  using G = InitGeo<DT>;
-  constexpr bool FAST = DT::kBF16;
-  constexpr int CAP = G::CAP;
-  __shared__ __attribute__((aligned(16))) T lds[(G::DBUF ? 2 : 1) * CAP * BLK];
+  __shared__ __attribute__((aligned(16))) float lds[INIT_CAP * BLK];
   const int lane = lane_id(), g = lane >> 4;
   if constexpr (GC) {
     if ((int)blockIdx.x < embed_blocks) {  // uniform per block
-      WPipe<T, G::NW, false, CAP> epipe(lds);
-      embed_block<DT>(ea, epipe, blockIdx.x, lane, g);
+      WPipe<float, InitGeo::NW, false, INIT_CAP> epipe(lds);
+      embed_block<F32T, InitGeo::NW>(ea, epipe, blockIdx.x, lane, g);
       return;
     }
   }
-  const int r = ((int)blockIdx.x - embed_blocks) * G::ROWS + (threadIdx.x >> 6) * ROWS_PER_WAVE + (lane & 15);
+  const int r = ((int)blockIdx.x - embed_blocks) * InitGeo::ROWS + (threadIdx.x >> 6) * ROWS_PER_WAVE + (lane & 15);
   const bool valid = r < a.Et;
   const int e = valid ? r : a.Et - 1;
-  const T* W = reinterpret_cast<const T*>(a.wmat);
-  WPipe<T, G::NW, G::DBUF, CAP> pipe(lds);
+  const float* W = reinterpret_cast<const float*>(a.wmat);
+  WPipe<float, InitGeo::NW, false, INIT_CAP> pipe(lds);
   pipe.issue(W + IE_T0 * BLK, 8);  // stage 0: the collapsed edge-message map (8 blocks)
 
   Act<2> geo;
   load_edge_geo(geo, a.edge_f + (int64_t)e * NFEAT_E, g);
-  Op<DT, 1> gop;
+  Op<F32T, 1> gop;
   make_op(gop, geo);
 
   // combined_linear_0 over [emb[src], emb[dst], em0, silu(d0), silu(r0), silu(o0), silu(a0)]
@@ -154,25 +151,25 @@ void k_init_edge(InitArgs a, EmbedArgs ea, int embed_blocks) {
   {
     // t = 0: edge_messages_linear_0 and its combined_linear_0 slice, collapsed on the host into one
     // [128, 2] map of the message columns (no activation between them, :237-241)
-    const T* w = pipe.next();
+    const float* w = pipe.next();
     pipe.issue(W + (IE_T0 + 40 * geo_t(0)) * BLK, 40);
     mma<8, 1>(acc, gop, w, lane);
   }
 #pragma unroll 1
   for (int i = 0; i < NT; ++i) {
-    const T* w = pipe.next();
+    const float* w = pipe.next();
     if (i + 1 < NT) pipe.issue(W + (IE_T0 + 40 * geo_t(i + 1)) * BLK, 40);
     else pipe.issue(W + IE_GEO1 * BLK, 40);
     Act<8> y;
     zero(y);
     mma<8, 1>(y, gop, w, lane);
-    silu2_<8, FAST>(y);
-    linear<DT, 8, 4>(acc, y, w + 8 * BLK, lane);
+    silu_<8, false>(y);
+    linear<F32T, 8, 4>(acc, y, w + 8 * BLK, lane);
   }
-  silu2_<8, FAST>(acc);  // combined_edge_logits (log2 units: feeds the gate product -> linear)
+  silu_<8, false>(acc);  // combined_edge_logits
   // gating: (em1 + silu(d1) + silu(r1) + silu(o1) + silu(a1)) * c
   {
-    const T* w = pipe.next();
+    const float* w = pipe.next();
     pipe.issue(W + IE_C1 * BLK, 16);
     Act<8> gs;
     if constexpr (GC) init_vec(gs, a.wvec + IEV_OGATE, g);  // silu(o1): constant; silu(r1) = 0
@@ -183,7 +180,7 @@ void k_init_edge(InitArgs a, EmbedArgs ea, int embed_blocks) {
       Act<8> y;
       zero(y);
       mma<8, 1>(y, gop, w + 8 * t * BLK, lane);
-      if (t > 0) silu2_<8, FAST>(y);
+      if (t > 0) silu_<8, false>(y);
       add_(gs, y);
     }
     mul_(acc, gs);
@@ -192,25 +189,25 @@ void k_init_edge(InitArgs a, EmbedArgs ea, int embed_blocks) {
   // combined_linear_2(combined_linear_1(.)) : 128 -> 28 (padded 32) -> 128
   Act<8> f;
   {
-    const T* w = pipe.next();
+    const float* w = pipe.next();
     if (with_fn) pipe.issue(W + IE_NBR * BLK, MAT128);
     Act<2> z;
     zero(z);
-    linear<DT, 2, 4>(z, acc, w, lane);
+    linear<F32T, 2, 4>(z, acc, w, lane);
     zero(f);
-    linear<DT, 8, 1>(f, z, w + 8 * BLK, lane);
+    linear<F32T, 8, 1>(f, z, w + 8 * BLK, lane);
   }
-  if (valid) store_edge_row(f, reinterpret_cast<T*>(a.f_out) + (int64_t)e * HID, g);
+  if (valid) store_edge_row(f, reinterpret_cast<float*>(a.f_out) + (int64_t)e * HID, g);
   if (!with_fn) return;
   // layer-0 silu(nbr_linear(F)), applied once per edge and gathered by the conformation module
   // (silu(nbr_linear(F[ids])) == silu(nbr_linear(F))[ids], deepinteract_modules.py:386-390)
   {
-    const T* w = pipe.next();
+    const float* w = pipe.next();
     Act<8> fn;
     init_vec(fn, a.wvec + IEV_NBR, g);
-    linear<DT, 8, 4>(fn, f, w, lane);
-    silu_<8, FAST>(fn);
-    if (valid) store_edge_row(fn, reinterpret_cast<T*>(a.fn_out) + (int64_t)e * HID, g);
+    linear<F32T, 8, 4>(fn, f, w, lane);
+    silu_<8, false>(fn);
+    if (valid) store_edge_row(fn, reinterpret_cast<float*>(a.fn_out) + (int64_t)e * HID, g);
   }
 }
 
@@ -220,8 +217,9 @@ constexpr int IR_NBLK = 128;  // resident weight blocks
 constexpr int IR_T0 = 0, IR_DIST = 8, IR_AMIDE = 48, IR_GATE = 88, IR_C = 112;
 
 // ================================================================ InitEdgeModule on 32x32x16 MFMA (bf16)
-// The arithmetic of k_init_edge<BF16T, GC> on 32-row tiles (csrc/mfma32.h): every 128-wide stage is
-// half the MFMAs of the 16x16 form, so half the MFMA hold on the SIMD's vector issue the SiLU-heavy
+// The bf16 InitEdge: k_init_edge's phases on 32-row tiles (csrc/mfma32.h) with bf16 operands and
+// log2-unit SiLUs (silu2_blk: the host packing scales the neighbouring weights). Every 128-wide stage is
+// half the MFMAs of a 16x16 chain, so half the MFMA hold on the SIMD's vector issue the SiLU-heavy
 // InitEdge is bound by (640 SiLU values per edge against 65,536 MAC). The bf16 init blob (kind 1) is
 // packed in the 32x32 fragment order (di_blob_layout(1, bf16) == 32). Geometric terms and gates are
 // produced one 32-feature block at a time (16 registers) and packed / multiplied straight away, so
@@ -342,7 +340,7 @@ __device__ __forceinline__ void geo_op32(P32<2>& gop, const float* edge_f, int e
   make_op32(gop, geo);
 }
 
-// staged weights (one 40-block slot per block, three blocks per CU, as k_init_edge); the first
+// staged weights (one INIT_CAP-block slot per block, three blocks per CU); the first
 // embed_blocks blocks run the node embedding (16x16 k_node_embed arithmetic, kind-0 blob)
 // <= 160 VGPRs (amdgpu_num_vgpr counts register pairs): three waves per SIMD hold 480 of the 512
 // registers, leaving exactly one 32-register pair-tensor wave room beside them. At 161 (168 allocated)
@@ -357,12 +355,11 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, InitX32Geo::THREADS), a
 void k_init_x32(InitArgs a, EmbedArgs ea, int embed_blocks) {
   static_assert(GC || !Z, "the z0 form is the DI_GRAPH_GEO_REF path");
   pq_signal_at_start(ea.sig_q, ea.sig_job);
-  using G = InitGeo<BF16T>;
   constexpr int NW = InitX32Geo::NW;
-  __shared__ __attribute__((aligned(16))) u16 lds[G::CAP * BLK];
+  __shared__ __attribute__((aligned(16))) u16 lds[INIT_CAP * BLK];
   const int lane = lane_id();
   if ((int)blockIdx.x < embed_blocks) {  // uniform per block
-    WPipe<u16, NW, false, G::CAP> epipe(lds);
+    WPipe<u16, NW, false, INIT_CAP> epipe(lds);
     embed_block<BF16T, NW>(ea, epipe, blockIdx.x, lane, lane >> 4);
     return;
   }
@@ -372,7 +369,7 @@ void k_init_x32(InitArgs a, EmbedArgs ea, int embed_blocks) {
   const bool valid = r < a.Et;
   const int e = valid ? r : a.Et - 1;
   const u16* W = reinterpret_cast<const u16*>(a.wmat);
-  WPipe<u16, NW, false, G::CAP> pipe(lds);
+  WPipe<u16, NW, false, INIT_CAP> pipe(lds);
   pipe.issue(W + IE_T0 * BLK, 8);
   P32<2> gop;
   geo_op32<GC>(gop, a.edge_f, e, h);
@@ -517,13 +514,13 @@ extern "C" int di_init_edge(const di_graph* g, di_dtype dt, const float* edge_f,
   InitArgs a{g->num_edges, edge_f, g->src, g->dst, g->node_pos, wmat, wvec, pos_src_tab, pos_dst_tab,
              f_out, fn_out};
   hipStream_t s = (hipStream_t)stream;
-  const dim3 gf = grid_of<InitGeo<F32T>>(a.Et), bf = block_of<InitGeo<F32T>>();
+  const dim3 gf = grid_of<InitGeo>(a.Et), bf = block_of<InitGeo>();
   const EmbedArgs ne{};
   const dim3 gx((unsigned)((a.Et + InitX32Geo::ROWS - 1) / InitX32Geo::ROWS)), bx(InitX32Geo::THREADS);
   if (dt == DI_BF16 && gc) hipLaunchKernelGGL((k_init_x32<true>), gx, bx, 0, s, a, ne, 0);
   else if (dt == DI_BF16) hipLaunchKernelGGL((k_init_x32<false>), gx, bx, 0, s, a, ne, 0);
-  else if (gc) hipLaunchKernelGGL((k_init_edge<F32T, true>), gf, bf, 0, s, a, ne, 0);
-  else hipLaunchKernelGGL((k_init_edge<F32T, false>), gf, bf, 0, s, a, ne, 0);
+  else if (gc) hipLaunchKernelGGL((k_init_edge<true>), gf, bf, 0, s, a, ne, 0);
+  else hipLaunchKernelGGL((k_init_edge<false>), gf, bf, 0, s, a, ne, 0);
   return launch_status();
 }
 
@@ -535,10 +532,9 @@ static void launch_embed_init(const InitArgs& a, const EmbedArgs& ea, hipStream_
     const int ib = (a.Et + InitX32Geo::ROWS - 1) / InitX32Geo::ROWS;
     hipLaunchKernelGGL((k_init_x32<true, Z>), dim3((unsigned)(eb + ib)), dim3(InitX32Geo::THREADS), 0, s, a, ea, eb);
   } else {
-    using G = InitGeo<DT>;
-    const int eb = (ea.Nt + G::ROWS - 1) / G::ROWS;
-    const int ib = (a.Et + G::ROWS - 1) / G::ROWS;
-    hipLaunchKernelGGL((k_init_edge<DT, true>), dim3((unsigned)(eb + ib)), block_of<G>(), 0, s, a, ea, eb);
+    const int eb = (ea.Nt + InitGeo::ROWS - 1) / InitGeo::ROWS;
+    const int ib = (a.Et + InitGeo::ROWS - 1) / InitGeo::ROWS;
+    hipLaunchKernelGGL((k_init_edge<true>), dim3((unsigned)(eb + ib)), block_of<InitGeo>(), 0, s, a, ea, eb);
   }
 }
 

@@ -16,7 +16,8 @@ namespace di {
 // in flight while this chunk's alphas and V rows land, so a chunk costs one memory latency; U rows
 // per lane in flight and 16 nodes per 256-thread block (grid = Nt / 16, several blocks per CU) hide
 // it. The products are added one edge at a time in edge order with the same fused multiply-adds as
-// the fused node kernel, so h_attn is bit-identical to what k_node_layer computes internally.
+// the fused node kernels (fp32: k_node_layer's node_gather; bf16: k_node_ws's seg_sum16), so h_attn is
+// bit-identical to what they compute internally.
 constexpr int AGG_NODES = 16;  // destinations per block (16 lanes each)
 template <class DT>
 struct AggrCfg {
@@ -124,18 +125,16 @@ __device__ __forceinline__ void attn_row(Act<8>& wv, const NodeArgs& a, int v, i
 
 // The CSR segment sum of one node held in the MFMA layout (wv[b][q] = feature 16b + 4g + q of node
 // v): wV / (z + 1e-6) with wV = sum alpha * V[src], z = sum alpha over v's in-edges
-// (deepinteract_modules.py:93-96, 116). Shared by the fused node layers (k_node_layer,
-// k_node_update_ring with attn == NULL); k_node_aggr computes the same products in the same order.
-template <class DT>
+// (deepinteract_modules.py:93-96, 116). The fp32 fused node layer's gather (k_node_layer with
+// attn == NULL); k_node_aggr computes the same products in the same order.
 __device__ __forceinline__ void node_gather(Act<8>& wv, const NodeArgs& a, int v, int g) {
-  using T = typename DT::T;
-  const T* qkv = reinterpret_cast<const T*>(a.qkv);
+  const float* qkv = reinterpret_cast<const float*>(a.qkv);
   zero(wv);
   floatx4 z = {0.f, 0.f, 0.f, 0.f};
   // In-edges in groups of UNR: the group's source ids, alphas and V[src] rows are all in flight
   // before the first product (one latency per group instead of two dependent ones per edge); the
   // products are still added one edge at a time in edge order (the reference's summation order).
-  constexpr int UNR = DT::kBF16 ? 4 : 2;
+  constexpr int UNR = 2;
   const int e0 = a.in_ptr[v], e1 = a.in_ptr[v + 1];
   int e = e0;
 #pragma unroll 1
@@ -144,7 +143,7 @@ __device__ __forceinline__ void node_gather(Act<8>& wv, const NodeArgs& a, int v
 #pragma unroll
     for (int u = 0; u < UNR; ++u) sid[u] = a.src[e + u];
     floatx4 al[UNR];
-    RawRow<T> vr[UNR];
+    RawRow<float> vr[UNR];
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       al[u] = ld4(a.alpha + (int64_t)(e + u) * 4);
@@ -179,13 +178,14 @@ __device__ __forceinline__ void node_gather(Act<8>& wv, const NodeArgs& a, int v
 // ================================================================ node update (bf16), 4-slot weight ring
 // O_node + residual + FFN (+ next layer's Q/K/V, + hT) from the aggregated rows of k_node_aggr.
 // Nt / 64 blocks is one block per CU, so a stage's 32 MFMAs per wave (~0.3 us) are far shorter than
-// an LDS-DMA stage's landing latency (~1 us): the double-buffered pipe of k_node_layer waits on
+// an LDS-DMA stage's landing latency (~1 us): a double-buffered WPipe would wait on
 // every stage. Here ALL the layer's biases land once at entry and the 32-KiB stages stream through
 // a 4-slot ring, three stages ahead: entering stage s the wave waits only for its own pieces of
 // stage s (s_waitcnt vmcnt(8 x stages issued after it): each wave issues exactly 8 one-KiB pieces
 // per stage, and every other vector-memory operation is older than them: outputs are held in
 // registers and stored at the end), then a barrier publishes the stage and frees the slot of
-// stage s-1 for stage s+3. Arithmetic identical to k_node_layer (same operands, same order).
+// stage s-1 for stage s+3. With k_node_aggr's rows it is bit-identical to k_node_ws
+// (tests/test_gpu_node_aggr.py).
 constexpr int NU_SLOTS = 4;
 constexpr int NU_STAGE = MAT128;  // blocks per stage
 __device__ __forceinline__ void nu_wait_younger(int n_stages_younger) {
@@ -385,8 +385,10 @@ constexpr int LDS_T = 2 * HID + 4;      // bf16 FFN-hidden rows: 130 words
 //     lanes = the block;
 //     (2) O_node + residual, FFN, Q|K|V as two 16-destination MFMA column groups, every register
 //     fragment feeding both groups, activations exchanged through LDS as bf16 operands.
-// Per output element the arithmetic is k_node_layer<BF16T>'s (the same bias + residual initial value,
-// the same k-steps in the same order, the same bf16 operands): h / Q,K,V / hT are bit-identical to it.
+// Per output element the arithmetic is that of k_node_aggr + k_node_update_ring (the same bias +
+// residual initial value, the same k-steps in the same order, the same bf16 operands): h / Q,K,V / hT
+// are bit-identical to the split pair (tests/test_gpu_node_aggr.py::
+// test_node_layer_ragged_csr_matches_split).
 constexpr int NWS_NW = 8;        // waves per block
 constexpr int NWS_TILE = 32;     // destinations per tile (2 MFMA column groups of 16)
 static_assert(NWS_TILE * 16 == 64 * NWS_NW, "16 aggregation lanes per destination of a tile");
@@ -515,7 +517,7 @@ void k_node_ws(NodeArgs a, int ntiles) {
       for (int b = 0; b < 2; ++b) put_slice(s_t, LDS_T, q, 16 * (2 * w + b), tq.v[b]);
     }
     __syncthreads();  // the hidden layer, all 256 features (and every wave is past its n operands)
-    // FFN output block w: both hidden halves in order, as k_node_layer
+    // FFN output block w: both hidden halves in order, as k_node_update_ring
 #pragma unroll
     for (int q = 0; q < NG; ++q) {
       Act<1> o;
@@ -573,49 +575,43 @@ void k_node_ws(NodeArgs a, int ntiles) {
   }
 }
 
-// ================================================================ fused node layer
-// Every bias vector rides in its stage's LDS slot (init_vec_lds) and the node's own input row is
-// added right after the stage barrier, before the next stage's DMA is issued: a global load
-// consumed after a DMA issue makes the wave wait for the whole in-flight weight stage (vmcnt
-// counts in order, and the compiler cannot count a runtime-length DMA loop), which exposed the
-// DMA latency at every stage.
-// Launch geometry of k_node_layer (di_node_layer, and di_node_update's fp32 path): DI_NODE_NW
-// waves (16 nodes each) per block. Round 2's 2-wave build faulted (code 719) because
-// di_node_update's fp32 launch kept a hard-coded 256-thread block while the kernel had been
-// compiled for 128 (__launch_bounds__(64 * 2)): every launch site now takes its shape from
-// NodeGeo. A C3 micro-batch has 16k nodes: 4-wave blocks give 250 blocks, 2-wave blocks 500
-// (measured beside the pair stream 58 vs 55 us per launch, so 4 is the default; the 2-wave build
-// is a tested variant, tools/build_variants.py "node2").
+// ================================================================ fused node layer (fp32)
+// The fp32 di_node_layer and di_node_update (the reference's precision; bf16: k_node_ws,
+// k_node_update_ring): each 64-KiB stage is DMA'd synchronously into ONE slot (pipe.next() issues
+// the stage, waits and publishes it). Every bias vector rides in its stage's slot (init_vec_lds),
+// and the node's own input row is loaded before the first stage and settled right after it, so no
+// later stage wait stands between the load and its use.
+// Launch geometry of k_node_layer: DI_NODE_NW waves (16 nodes each) per block. Round 2's 2-wave
+// build faulted (code 719) because di_node_update's fp32 launch kept a hard-coded 256-thread block
+// while the kernel had been compiled for 128 (__launch_bounds__(64 * 2)): every launch site now
+// takes its shape from NodeGeo. 4 waves is the default; the 2-wave build of the fp32 node layer is
+// a tested variant (tools/build_variants.py "node2").
 #ifndef DI_NODE_NW
 #define DI_NODE_NW 4
 #endif
 using NodeGeo = KernelGeo<DI_NODE_NW>;
-template <class DT, bool FINAL>
+template <bool FINAL>
 __global__ __launch_bounds__(NodeGeo::THREADS, 2) void k_node_layer(NodeArgs a) {
-  using T = typename DT::T;
-  constexpr bool FAST = DT::kBF16;
-  constexpr bool DB = DT::kBF16;
-  using Pipe = WPipe<T, NodeGeo::NW, DB, MAT128, 128>;
-  __shared__ __attribute__((aligned(16))) char lds[(DB ? 2 : 1) * Pipe::SLOT_BYTES];
+  using Pipe = WPipe<float, NodeGeo::NW, false, MAT128, 128>;
+  __shared__ __attribute__((aligned(16))) char lds[Pipe::SLOT_BYTES];
   const int lane = lane_id(), g = lane >> 4;
   const int r = row_id<NodeGeo::NW>();
   const bool valid = r < a.Nt;
   const int v = valid ? r : a.Nt - 1;
-  const T* W = reinterpret_cast<const T*>(a.wmat);
+  const float* W = reinterpret_cast<const float*>(a.wmat);
   const float* V = a.wvec;
-  const T* qkv = reinterpret_cast<const T*>(a.qkv);
   Pipe pipe(lds);
   pipe.issue(W + NL_ON * BLK, MAT128, V + NLV_ON, 128);
-  RawRow<T> hin;  // in1 of the residual, consumed after the O stage barrier
-  hin.load(reinterpret_cast<const T*>(a.h_in) + (int64_t)v * HID, g);
+  RawRow<float> hin;  // in1 of the residual, consumed after the O stage barrier
+  hin.load(reinterpret_cast<const float*>(a.h_in) + (int64_t)v * HID, g);
 
   // send_and_recv(u_mul_e('V_h','score'), sum) and (copy_e('score'), sum); h = wV / (z + 1e-6)
   Act<8> wv;
   if (a.attn != nullptr) attn_row(wv, a, v, g);  // k_node_aggr (same products, order, division) or the fold
-  else node_gather<DT>(wv, a, v, g);
+  else node_gather(wv, a, v, g);
   // n = in1 + O_node(h)
-  const T* w = pipe.next();
-  settle(hin);  // landed with the O stage (the barrier drained vmcnt); no wait on the F1 DMA later
+  const float* w = pipe.next();
+  settle(hin);  // landed with the O stage (its wait drained vmcnt)
   pipe.issue(W + NL_F1 * BLK, MAT128, V + NLV_F1, 128);
   Act<8> n;
   init_vec_lds(n, pipe.v(), g);
@@ -624,7 +620,7 @@ __global__ __launch_bounds__(NodeGeo::THREADS, 2) void k_node_layer(NodeArgs a) 
     hin.to_act(hv);
     add_(n, hv);
   }
-  linear<DT, 8, 4>(n, wv, w, lane);
+  linear<F32T, 8, 4>(n, wv, w, lane);
   // n = n + W2 silu(W1 BN2(n))
   Act<8> o;
   zero(o);
@@ -634,35 +630,31 @@ __global__ __launch_bounds__(NodeGeo::THREADS, 2) void k_node_layer(NodeArgs a) 
     pipe.issue(W + (NL_F2 + MAT128 * half) * BLK, MAT128);
     Act<8> t;
     init_vec_lds(t, pipe.v(), g);
-    linear<DT, 8, 4>(t, n, w, lane);
-    silu2_<8, FAST>(t);
+    linear<F32T, 8, 4>(t, n, w, lane);
+    silu_<8, false>(t);
     w = pipe.next();
     if (half == 0) pipe.issue(W + (NL_F1 + MAT128) * BLK, MAT128, V + NLV_F1 + 128, 128);
     else if (!FINAL) pipe.issue(W + NL_Q * BLK, MAT128, V + NLV_Q, 128);
-    linear<DT, 8, 4>(o, t, w, lane);
+    linear<F32T, 8, 4>(o, t, w, lane);
   }
   add_(n, o);
-  if (valid) store_row(n, reinterpret_cast<T*>(a.h_out) + (int64_t)v * HID, g);
-  if (a.hT_out != nullptr && valid) {  // 16 lanes (nodes) store 32 contiguous bytes per feature
-    T* hT = reinterpret_cast<T*>(a.hT_out);
+  if (valid) store_row(n, reinterpret_cast<float*>(a.h_out) + (int64_t)v * HID, g);
+  if (a.hT_out != nullptr && valid) {  // 16 lanes (nodes) store 64 contiguous bytes per feature
+    float* hT = reinterpret_cast<float*>(a.hT_out);
 #pragma unroll
     for (int b = 0; b < 8; ++b)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float x = n.v[b][q];
-        if constexpr (DT::kBF16) hT[(int64_t)(16 * b + 4 * g + q) * a.Nt + v] = (u16)(pack_bf16x2(x, 0.f) & 0xffffu);
-        else hT[(int64_t)(16 * b + 4 * g + q) * a.Nt + v] = x;
-      }
+      for (int q = 0; q < 4; ++q) hT[(int64_t)(16 * b + 4 * g + q) * a.Nt + v] = n.v[b][q];
   }
   if constexpr (!FINAL) {
-    T* qo = reinterpret_cast<T*>(a.qkv_out);
+    float* qo = reinterpret_cast<float*>(a.qkv_out);
 #pragma unroll 1
     for (int q = 0; q < 3; ++q) {
       w = pipe.next();
       if (q < 2) pipe.issue(W + (NL_Q + MAT128 * (q + 1)) * BLK, MAT128, V + NLV_Q + 128 * (q + 1), 128);
       Act<8> t;
       init_vec_lds(t, pipe.v(), g);
-      linear<DT, 8, 4>(t, n, w, lane);
+      linear<F32T, 8, 4>(t, n, w, lane);
       if (valid) store_row(t, qo + (int64_t)v * 3 * HID + q * HID, g);
     }
   }
@@ -692,8 +684,8 @@ extern "C" int di_node_layer(const di_graph* g, di_dtype dt, int final_layer, co
     if (final_layer) hipLaunchKernelGGL((k_node_ws<true>), p.grid, bw, 0, s, a, p.ntiles);
     else hipLaunchKernelGGL((k_node_ws<false>), p.grid, bw, 0, s, a, p.ntiles);
   } else {
-    if (final_layer) hipLaunchKernelGGL((k_node_layer<F32T, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_node_layer<F32T, false>), grid, block, 0, s, a);
+    if (final_layer) hipLaunchKernelGGL((k_node_layer<true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_node_layer<false>), grid, block, 0, s, a);
   }
   return launch_status();
 }
@@ -725,8 +717,8 @@ static int node_update(const di_graph* g, di_dtype dt, int final_layer, const fl
     else hipLaunchKernelGGL((k_node_update_ring<false>), grid, block, 0, s, a);
   } else {
     const dim3 grid = grid_of<NodeGeo>(a.Nt), block = block_of<NodeGeo>();
-    if (final_layer) hipLaunchKernelGGL((k_node_layer<F32T, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_node_layer<F32T, false>), grid, block, 0, s, a);
+    if (final_layer) hipLaunchKernelGGL((k_node_layer<true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_node_layer<false>), grid, block, 0, s, a);
   }
   return launch_status();
 }

@@ -153,13 +153,6 @@ __device__ __forceinline__ void init_vec32(X32<NB>& a, const float* vec, int h) 
 #pragma unroll
     for (int q = 0; q < 4; ++q) set_quad(a.v[b], q, ld4(vec + 32 * b + 8 * q + 4 * h));
 }
-template <int NB>
-__device__ __forceinline__ void to_x32(X32<NB>& a, const R32<NB>& r) {
-#pragma unroll
-  for (int b = 0; b < NB; ++b)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) set_quad(a.v[b], q, unpack4(r.u[4 * b + q]));
-}
 // the row's bf16 bytes, written by the lanes with `valid`; 16 B per lane: quads 2j, 2j+1 swapped
 // between the row's two lanes (the mirror image of R32::unswz), then lane (row, h) stores quad
 // 2j + h of both halves at bytes 32 j + 16 h. Called by the whole wave: the swaps run with every

@@ -2,8 +2,9 @@
 next to the product library) on the GPU, each in a child process that binds the variant instead of
 the product build (deepinteract_amd._lib.load_variant):
 
-* ``node2`` (DI_NODE_NW=2: k_node_layer in 2-wave blocks -- the round-2 fault's build): split vs
-  fused node layer bit-identical in fp32 and bf16 on the c2 fixture, GeoT outputs vs the fixture;
+* ``node2`` (DI_NODE_NW=2: the fp32 node layer, k_node_layer, in 2-wave blocks -- the round-2
+  fault's build; the bf16 node kernels do not read the knob): split vs fused node layer
+  bit-identical in fp32 and bf16 on the c2 fixture, GeoT outputs vs the fixture;
 * ``f32exact`` (DI_F32_FAST_SILU=0: fp32 SiLU as libm expf + IEEE division, the exact form the
   default build replaces with v_exp / v_rcp): fp32 GeoT node / edge outputs of tiny / c1 / c2 vs the
   reference's golden vectors within north_star's 1e-4.

@@ -10,8 +10,9 @@ from deepinteract_amd import build
 
 VARIANTS = {
     # the product library's compile-time knobs, each kept tested by a -m gpu test against its variant:
-    # k_node_layer in 2-wave blocks (csrc/geot_node.hip DI_NODE_NW; every launch site takes its shape
-    # from NodeGeo; tests/test_gpu_variants.py, tests/test_gpu_node_aggr.py via DI_TEST_VARIANT)
+    # the fp32 node layer (k_node_layer) in 2-wave blocks (csrc/geot_node.hip DI_NODE_NW; every launch
+    # site takes its shape from NodeGeo; the bf16 node kernels do not read the knob;
+    # tests/test_gpu_variants.py, tests/test_gpu_node_aggr.py via DI_TEST_VARIANT)
     "node2": ["DI_NODE_NW=2"],
     # fp32 SiLU as libm expf + IEEE division (csrc/common.h DI_F32_FAST_SILU; the round-2 default)
     "f32exact": ["DI_F32_FAST_SILU=0"],

@@ -10,7 +10,7 @@ import sys
 
 R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 defs = [a for a in sys.argv[1:] if a.startswith("-D")]
-kre = re.compile(sys.argv[sys.argv.index("--kernel") + 1] if "--kernel" in sys.argv else r"k_edge_layerINS_5BF16TELi0E")
+kre = re.compile(sys.argv[sys.argv.index("--kernel") + 1] if "--kernel" in sys.argv else r"k_edge_x32_ringILi0ELb1ELb0E")
 stage = sys.argv[sys.argv.index("--stage") + 1] if "--stage" in sys.argv else "edge"
 out = "/tmp/isa_view.s"
 subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--offload-device-only", "-S",

@@ -155,12 +155,12 @@ constexpr int LDS_T = 2 * HID + 8;""", 1)],
     # the edge ring's weight stages DMA'd at half their blocks (the slot's second half keeps stale
     # weights; timing only): how much of the edge layers' cost to the pair stream is their L2 -> LDS
     # weight stream (~16 TB/s of L2 reads chip-wide while the ring runs)
-    "whalf": [("geot_edge.hip", "    return {W, {EL_ORDER[si], 0, 0}, {EL_SIZE[si], 0, 0}, 1, vo >= 0 ? V + vo : nullptr};",
-               "    return {W, {EL_ORDER[si], 0, 0}, {EL_SIZE[si] / 2, 0, 0}, 1, vo >= 0 ? V + vo : nullptr};", 1)],
+    "whalf": [("geot_edge.hip", "    const int off = EL_ORDER[si], n = EL_SIZE[si];  // the stage's run: first block, block count",
+               "    const int off = EL_ORDER[si], n = EL_SIZE[si] / 2;", 1)],
     # the edge ring's weight stages all DMA'd from the blob's first blocks (same bytes, a 36-KiB
     # footprint that always hits L2; timing only): separates the stream's L2 misses from its bytes
-    "ringw0": [("geot_edge.hip", "    return {W, {EL_ORDER[si], 0, 0}, {EL_SIZE[si], 0, 0}, 1, vo >= 0 ? V + vo : nullptr};",
-                "    return {W, {0, 0, 0}, {EL_SIZE[si], 0, 0}, 1, vo >= 0 ? V + vo : nullptr};", 1)],
+    "ringw0": [("geot_edge.hip", "    const int off = EL_ORDER[si], n = EL_SIZE[si];  // the stage's run: first block, block count",
+                "    const int off = 0, n = EL_SIZE[si];", 1)],
     # the edge ring's blocks of one XCD kept in step: after each tile (but a block's last ones), wave 0
     # adds to its XCD's counter and waits (<= 20 us) until every block of the XCD has finished that
     # tile, so the 32 blocks stay within one tile of each other and fewer of the layer's weight stages
