@@ -91,6 +91,23 @@ class DiHeadItem(ctypes.Structure):
                 ("w", ctypes.c_int32)]
 
 
+class DiHeadBlock(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in
+                ("w1", "w2", "w3", "gamma1", "beta1", "gamma2", "beta2", "gamma3", "beta3", "bias1", "bias2",
+                 "bias3", "se_w1", "se_b1", "se_w2", "se_b2")] + [("eps", ctypes.c_float), ("dilation", ctypes.c_int32)]
+
+
+class DiHeadNet(ctypes.Structure):
+    _fields_ = [("proj_w", ctypes.c_void_p), ("proj_b", ctypes.c_void_p), ("blocks", ctypes.POINTER(DiHeadBlock)),
+                ("num_blocks", ctypes.c_int32), ("in_elu", ctypes.c_int32)]
+
+
+class DiHeadArena(ctypes.Structure):
+    _fields_ = [("wide0", ctypes.c_void_p), ("wide1", ctypes.c_void_p), ("half0", ctypes.c_void_p),
+                ("half1", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("rows", ctypes.c_void_p),
+                ("items", ctypes.c_void_p), ("items_dev", ctypes.c_void_p), ("count", ctypes.c_int32)]
+
+
 # pair-queue words (include/deepinteract_amd.h, di_pair_queue_bytes)
 PQ_READY, PQ_ERROR, PQ_GAVE_UP, PQ_SBYTES, PQ_HBYTES = 0, 32, 33, 40, 42
 
@@ -146,6 +163,10 @@ _SIGS = {
     "di_head_norm_fold_batch": ([_P, _I, _P, _P, _I, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P], ctypes.c_int),
     "di_se_scale_add_batch": ([_I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P], ctypes.c_int),
     "di_se_gate": ([_P, _P, _P, _P, _P, _I, _I, _I, _P, _P], ctypes.c_int),
+    "di_head_body_batch": ([_I, ctypes.POINTER(DiHeadNet), _I, ctypes.POINTER(DiHeadArena),
+                            ctypes.POINTER(ctypes.c_int32), _P], ctypes.c_int),
+    "di_head_body_batch_check": ([_I, ctypes.POINTER(DiHeadNet), _I, ctypes.POINTER(DiHeadArena)], ctypes.c_int),
+    "di_head_logits_batch": ([_I, _P, _P, _P, _P, _P, _I, _P, _P], ctypes.c_int),
     "di_contact_rank_work_bytes": ([ctypes.c_int64, _I], ctypes.c_int64),
     "di_contact_rank": ([_I, _P, _I, _I, _I, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
     "di_contact_auc_work_bytes": ([ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),

@@ -62,21 +62,7 @@ struct HcArgs {
   int32_t cin, h, wd, dil, in_elu;
 };
 
-// ELU. The negative branch expm1(z) to ~1e-6 relative in a dozen VALU operations (libm's expm1f, at
-// several times that, was a quarter of the fused kernels' time): the degree-6 Taylor polynomial for
-// z > -0.25 (remainder z^6 / 5040 < 5e-8 relative) and exp(z) - 1 with the hardware exponential below
-// it (|result| >= 0.22, so the absolute ~1e-7 is ~5e-7 relative). The value is rounded to bf16
-// (2^-9 relative) next.
-__device__ __forceinline__ float hc_elu(float z) {
-  float p = fmaf(z, 1.f / 720.f, 1.f / 120.f);
-  p = fmaf(z, p, 1.f / 24.f);
-  p = fmaf(z, p, 1.f / 6.f);
-  p = fmaf(z, p, 0.5f);
-  p = fmaf(z, p, 1.f);
-  p *= z;
-  const float e = __expf(z) - 1.f;
-  return z > 0.f ? z : (z > -0.25f ? p : e);
-}
+// hc_elu (the fused ELU): head_batch.h, shared with the logits kernel of head_body.hip
 // v + (v of the lane a DPP pattern pairs this one with), for the reduction over a row of 16 lanes:
 // quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror in turn leave every lane of
 // the row with the row's sum (after each step the lanes of a quad / half hold one value, and the next

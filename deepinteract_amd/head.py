@@ -531,10 +531,21 @@ class ResNet2DInputWithOptAttention(nn.Module):
         return self.phase2_conv(x)
 
 
-    def body_batch(self, xs):
+    def plan(self, check="all"):
+        """This head's HeadBodyPlan, rebuilt when a parameter it points into was replaced or written
+        (HeadBodyPlan.stale; check="head": only those the first launches read)."""
+        plan = getattr(self, "_plan", None)
+        if plan is None or plan.ops is not self.ops or plan.stale(check):
+            plan = self._plan = HeadBodyPlan(self, self.ops)
+        return plan
+
+    def body_batch(self, xs, native=False):
         """body for several images in one launch sequence (bf16, HIP convolutions): xs is a list of
         [1, 128, h, w] prologue outputs, or a HeadBatch whose ``input(i)`` views hold them. Returns
-        the list of logits. Each image's logits are the same bits whatever else the batch holds."""
+        the list of logits. Each image's logits are the same bits whatever else the batch holds.
+        native: the same launches issued from C (di_head_body_batch, called on the plan's two parts) and
+        phase2_conv(ELU(x)) of all images by one HIP launch (di_head_logits_batch) instead of two torch
+        kernels per image; the logits are views of one packed buffer."""
         if getattr(self, "cops", None) is None or self.ops is None:
             raise RuntimeError("body_batch needs the HIP convolutions and norm passes (use_hip_convs, "
                                "use_hip_norm_ops)")
@@ -544,9 +555,160 @@ class ResNet2DInputWithOptAttention(nn.Module):
             hb = HeadBatch([x.shape[2:] for x in xs], xs[0].device)
             for i, x in enumerate(xs):
                 hb.input(i).copy_(x)
+        if native:
+            # the staleness check reads ~850 parameters' pointers and versions (~0.25 ms): only those of the
+            # first launches are checked before anything runs, the rest while the GPU works on these
+            plan = self.plan(check="head")
+            which = plan.body(hb, part=0)
+            plan = self.plan()
+            return plan.logits(hb, hb.wide[plan.body(hb, part=1, start=which)])
         x, spare = self.base_resnet._forward_hipconv_batch(hb, hb.wide[0], hb.wide[1], self.ops, self.cops)
         x, spare = self.phase2_resnet._forward_hipconv_batch(hb, x, spare, self.ops, self.cops, in_elu=True)
         return [self.phase2_conv(F.elu(hb.view(x, hb.CHANNELS, i))) for i in range(hb.count)]
+
+
+class HeadBodyPlan:
+    """The head's body as di_head_body_batch takes it (include/deepinteract_amd.h): one di_head_net per
+    ResNet with its host array of di_head_block, every pointer into the module's own bf16 tensors or into
+    HeadNormOps.f32's cached fp32 copies, plus phase2_conv as di_head_logits_batch's fp32 [2, 128] rows.
+    Built once from a ResNet2DInputWithOptAttention and rebuilt by ``ResNet2DInputWithOptAttention.plan()``
+    when ``stale()``: a parameter's storage or ``_version`` changed (a reload, a dtype or device move).
+    ``nets`` is the table a C caller would pass; ``parts`` cuts the same blocks after the first HEAD of
+    them, so that a forward can start on part 0 and check the other parameters meanwhile.
+    No GPU is needed to build one (``ops`` None: the fp32 copies are made here); running it needs the
+    bf16 head on the GPU."""
+
+    HEAD = 3   # blocks of part 0: ~30 launches, what the full check's ~0.25 ms hide behind
+
+    def __init__(self, head, ops=None):
+        from . import _lib
+        self._lib, self.ops = _lib, ops
+        f32 = ops.f32 if ops is not None else (lambda p: None if p is None else p.detach().float().contiguous())
+        self._params, self._keep, self._weights = [], [], []
+        self.blocks, self.dilations = [], []
+        nets, parts = [], []
+        for net, in_elu in ((head.base_resnet, False), (head.phase2_resnet, True)):
+            m = net._modules
+            proj = m[f"resnet_{net.module_name}_init_proj"] if net.initial_projection else None
+            if in_elu and proj is None:
+                raise NotImplementedError("a batched ResNet applies the caller's ELU in its initial projection")
+            pw = self._own(proj.weight) if proj is not None else None
+            pb = self._vec(proj.bias, f32) if proj is not None else None
+            arr = (_lib.DiHeadBlock * len(net.blocks))()
+            for at, (blk, r) in enumerate(zip(arr, net.blocks)):
+                if not nets and at == self.HEAD:
+                    self._n_head = len(self._params)
+                convs = [m[f"{r}_conv2d_{i}"] for i in (1, 2, 3)]
+                se = m[f"{r}_se_block"]
+                C = convs[0].weight.shape[1]
+                hidden = se.linear1.weight.shape[0]
+                want = [(C // 2, C, 1, 1), (C // 2, C // 2, 3, 3), (C, C // 2, 1, 1)]
+                if C != HeadBatch.CHANNELS or hidden != 8 or [tuple(c.weight.shape) for c in convs] != want:
+                    raise ValueError(f"{r}: di_head_body_batch runs 128-channel bottleneck blocks with an 8-unit SE")
+                blk.w1, blk.w2, blk.w3 = (self._own(c.weight) for c in convs)
+                if net.inorm:
+                    norms = [m[f"{r}_inorm_{i}"] for i in (1, 2, 3)]
+                    if len({n.eps for n in norms}) != 1:
+                        raise ValueError(f"{r}: one eps per block")
+                    blk.eps = norms[0].eps
+                    for i, n in enumerate(norms, 1):
+                        setattr(blk, f"gamma{i}", self._vec(n.weight, f32))
+                        setattr(blk, f"beta{i}", self._vec(n.bias, f32))
+                else:
+                    blk.eps = 0.0
+                    blk.bias1, blk.bias2 = self._vec(convs[0].bias, f32), self._vec(convs[1].bias, f32)
+                blk.bias3 = self._vec(convs[2].bias, f32)
+                blk.se_w1, blk.se_b1, blk.se_w2, blk.se_b2 = (self._vec(p, f32) for p in (
+                    se.linear1.weight, se.linear1.bias, se.linear2.weight, se.linear2.bias))
+                blk.dilation = convs[1].dilation[0]
+                self.dilations.append(blk.dilation)
+            self.blocks.append(arr)
+            if not nets and len(arr) > self.HEAD:   # the first net in two parts: [0, HEAD) and the rest
+                rest = ctypes.cast(ctypes.byref(arr, self.HEAD * ctypes.sizeof(_lib.DiHeadBlock)),
+                                   ctypes.POINTER(_lib.DiHeadBlock))
+                parts += [_lib.DiHeadNet(pw, pb, arr, self.HEAD, int(in_elu)),
+                          _lib.DiHeadNet(None, None, rest, len(arr) - self.HEAD, 0)]
+            else:
+                if not nets:
+                    self._n_head = len(self._params)
+                parts.append(_lib.DiHeadNet(pw, pb, arr, len(arr), int(in_elu)))
+            nets.append(_lib.DiHeadNet(pw, pb, arr, len(arr), int(in_elu)))
+        self.nets = (_lib.DiHeadNet * len(nets))(*nets)
+        self.parts = ((_lib.DiHeadNet * 1)(parts[0]), (_lib.DiHeadNet * (len(parts) - 1))(*parts[1:]))
+        p2 = head.phase2_conv
+        if tuple(p2.weight.shape) != (2, HeadBatch.CHANNELS, 1, 1):
+            raise ValueError("di_head_logits_batch computes 2 classes from 128 channels")
+        self.logit_w, self.logit_b = self._vec(p2.weight, f32), self._vec(p2.bias, f32)
+        self.num_blocks = len(self.dilations)
+        w = self._weights
+        self.device = w[0].device
+        self.runnable = all(t.dtype == torch.bfloat16 and t.is_contiguous() and t.device == self.device for t in w)
+        self._sig = self._signature(len(self._params))
+
+    def __deepcopy__(self, memo):
+        return None   # raw pointers: a copied or unpickled module builds its own plan
+
+    def __reduce__(self):
+        return (type(None), ())
+
+    def _own(self, p):
+        """A pointer into the module's own tensor."""
+        self._params.append(p)
+        self._weights.append(p)
+        return p.data_ptr()
+
+    def _vec(self, p, f32):
+        """A pointer to the fp32 copy of a parameter (None: NULL)."""
+        if p is None:
+            return None
+        self._params.append(p)
+        t = f32(p)
+        self._keep.append(t)
+        return t.data_ptr()
+
+    def _signature(self, n):
+        ps = self._params[:n]
+        return [p.data_ptr() for p in ps], [p._version for p in ps]
+
+    def stale(self, check="all"):
+        """Whether a parameter the tables point into (check="head": into part 0's) has another storage
+        or version than when the plan was built."""
+        n = self._n_head if check == "head" else len(self._params)
+        ptrs, versions = self._signature(n)
+        return ptrs != self._sig[0][:n] or versions != self._sig[1][:n]
+
+    def arena(self, hb, start=0):
+        """The batch's buffers, with hb.wide[start] as the input."""
+        return self._lib.DiHeadArena(hb.wide[start].data_ptr(), hb.wide[start ^ 1].data_ptr(), hb.half[0].data_ptr(),
+                                     hb.half[1].data_ptr(), hb.stats.data_ptr(), hb.rows.data_ptr(),
+                                     ctypes.addressof(hb.items), hb.items_ptr.value, hb.count)
+
+    def body(self, hb, part=None, start=0):
+        """di_head_body_batch over a HeadBatch whose wide[start] holds the input -- the whole body, or
+        part 0 / part 1 of it: the index of the hb.wide buffer holding the result."""
+        _lib = self._lib
+        if not self.runnable or hb.device != self.device:
+            raise ValueError("di_head_body_batch takes the modules' contiguous bf16 weights on the batch's device")
+        nets = self.nets if part is None else self.parts[part]
+        arena, which = self.arena(hb, start), ctypes.c_int32(-1)
+        _lib.check(_lib.load().di_head_body_batch(_lib.DI_BF16, nets, len(nets), ctypes.byref(arena),
+                                                  ctypes.byref(which), _stream()), "di_head_body_batch")
+        return start ^ which.value
+
+    def logits(self, hb, x):
+        """phase2_conv(ELU(x)) of a packed 128-channel buffer (di_head_logits_batch): the [1, 2, h, w]
+        views of one new packed bf16 buffer."""
+        _lib = self._lib
+        hb.check_packed(x, hb.CHANNELS)
+        y = torch.empty(2 * hb.pixels, dtype=torch.bfloat16, device=hb.device)
+        _lib.check(_lib.load().di_head_logits_batch(_lib.DI_BF16, _ptr(x), self.logit_w, self.logit_b, hb.items,
+                                                    hb.items_ptr, hb.count, _ptr(y), _stream()),
+                   "di_head_logits_batch")
+        return [hb.view(y, 2, i) for i in range(hb.count)]
+
+    def run(self, hb):
+        """The body, then the logits: two C calls and one allocation, whatever the batch holds."""
+        return self.logits(hb, hb.wide[self.body(hb)])
 
 
 def contact_probs(logits):

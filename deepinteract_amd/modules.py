@@ -87,7 +87,7 @@ class LitGINI(nn.Module):
                  num_classes=2, max_num_graph_nodes=NODE_COUNT_LIMIT, max_num_residues=RESIDUE_COUNT_LIMIT,
                  dtype="f32", head_dtype=torch.float32, precise_head=False, fuse_head_prologue=False,
                  head_channels_last=False, head_hip_ops=True, head_convs="torch", pos_prob_threshold=0.5,
-                 head_batch=0, head_batch_pixels=2 ** 22, **kwargs):
+                 head_batch=0, head_batch_pixels=2 ** 22, head_body="python", **kwargs):
         super().__init__()
         if num_gnn_hidden_channels != 128 or num_gnn_attention_heads != 4:
             # Q/K/V are Linear(H, H) whatever the head count, so a checkpoint trained with another
@@ -137,6 +137,17 @@ class LitGINI(nn.Module):
         if head_batch > 0 and head_convs != "hip":
             raise ValueError('head_batch > 0 needs head_convs="hip" (the batched head runs on the HIP convolutions)')
         self.head_batch, self.head_batch_pixels = head_batch, head_batch_pixels
+        # head_body: "python" issues the batched head's launches from ResNet._forward_hipconv_batch;
+        # "native" issues the same launches from one C call per chunk (di_head_body_batch) and takes the
+        # logits from one HIP launch (di_head_logits_batch). Same bits up to phase2_conv's input; it takes
+        # the interpreter out from between the ~600 launches, which is worth 9 % on one 64 x 64 complex and
+        # about nothing from 145 x 145 up, where the kernels' own time is the floor.
+        # With head_batch=0 every complex goes through as a chunk of one.
+        if head_body not in ("python", "native"):
+            raise ValueError(f'head_body must be "python" or "native", got {head_body!r}')
+        if head_body == "native" and head_convs != "hip":
+            raise ValueError('head_body="native" needs head_convs="hip" (it runs the HIP convolutions\' launches)')
+        self.head_body = head_body
         self.max_num_residues = max_num_residues
         # pos_prob_threshold: a contact is predicted where its probability reaches it (test_step's
         # rounded predictions and confusion counts; the reference's default)
@@ -209,7 +220,7 @@ class LitGINI(nn.Module):
                                + "; ".join(problems[:8]))
         opts = {k: kwargs[k] for k in ("dtype", "head_dtype", "precise_head", "fuse_head_prologue",
                                        "head_channels_last", "head_hip_ops", "head_convs", "head_batch",
-                                       "head_batch_pixels") if k in kwargs}
+                                       "head_batch_pixels", "head_body") if k in kwargs}
         model = cls(num_node_input_feats=cfg.num_node_input_feats, num_gnn_layers=cfg.num_gnn_layers,
                     num_gnn_hidden_channels=cfg.num_gnn_hidden_channels,
                     num_gnn_attention_heads=cfg.num_gnn_attention_heads, knn=cfg.knn,
@@ -277,21 +288,25 @@ class LitGINI(nn.Module):
         h2r = [off[b] for _, b in pairs]
         l1 = [gb.nodes_per_graph[a] for a, _ in pairs]
         l2 = [gb.nodes_per_graph[b] for _, b in pairs]
-        if prologue_op is not None:
+        batched = self.head_batch > 0 or self.head_body == "native"
+        if prologue_op is not None and self.head_body == "native" and h.dtype == torch.bfloat16:
+            logits = self._head_native_fused(prologue_op, h, h1r, h2r, l1, l2)
+        elif prologue_op is not None:
             _, views = prologue_op(h, h1r, h2r, l1, l2)
-            logits = self._head_batched(views, True) if self.head_batch > 0 else \
+            logits = self._head_batched(views, True) if batched else \
                 [self.interact_forward(v, prologue_done=True) for v in views]
         else:
             _, views = pair_op(h, h1r, h2r, l1, l2, hT=eng.last_hT)
-            logits = self._head_batched(views, False) if self.head_batch > 0 else \
+            logits = self._head_batched(views, False) if batched else \
                 [self.interact_forward(v) for v in views]
         return logits, h, e
 
     def _head_chunks(self, shapes):
         """Consecutive complexes in chunks of at most head_batch complexes and head_batch_pixels pixels."""
         chunks, cur, px = [], [], 0
+        most = max(1, self.head_batch)  # head_batch=0 with head_body="native": chunks of one
         for i, (a, b) in enumerate(shapes):
-            if cur and (len(cur) == self.head_batch or px + a * b > self.head_batch_pixels):
+            if cur and (len(cur) == most or px + a * b > self.head_batch_pixels):
                 chunks.append(cur)
                 cur, px = [], 0
             cur.append(i)
@@ -315,7 +330,19 @@ class LitGINI(nn.Module):
                         hb.input(slot).copy_(views[i])
                     else:
                         im.ops.inorm_elu(im.conv2d_1(views[i].to(self.head_dtype)), im.inorm_1, out=hb.input(slot))
-                logits += im.body_batch(hb)
+                logits += im.body_batch(hb, native=self.head_body == "native")
+        return logits
+
+    def _head_native_fused(self, prologue_op, h, h1r, h2r, l1, l2):
+        """head_body="native" behind the fused prologue on bf16 node features: HeadPrologueOp writes a
+        whole chunk straight into its arena's input buffer (its packed C * L1 * L2 offsets are the
+        HeadBatch layout), so a chunk is three C calls and no per-complex launch or copy."""
+        im = self.interact_module
+        logits = []
+        for chunk in self._head_chunks(list(zip(l1, l2))):
+            hb = HeadBatch([(l1[i], l2[i]) for i in chunk], h.device)
+            prologue_op(h, *([v[i] for i in chunk] for v in (h1r, h2r, l1, l2)), out=hb.wide[0])
+            logits += im.body_batch(hb, native=True)
         return logits
 
     def predict_batch(self, gb: GraphBatch, pairs):

@@ -24,6 +24,8 @@
  *   di_inorm_elu    ELU(InstanceNorm2d(x)) of the head's ResNet blocks deepinteract_modules.py:1016-1030,1075-1095
  *   di_se_scale_add conv bias + SEBlock gate + residual add          deepinteract_modules.py:954-970, 1095
  *   di_channel_mean SEBlock squeeze (channel mean)                   deepinteract_modules.py:966
+ *   di_head_body_batch  the head's two ResNets for a batch of complexes deepinteract_modules.py:1234-1241
+ *   di_head_logits_batch  phase2_conv(ELU(x)) for the batch           deepinteract_modules.py:1241, 1247
  *   di_knn_topk     dgl.knn_graph + topk(pairwise_squared_distance)  graph_utils.py:107-108
  *   di_knn_graph    knn_graph's edge list / in-edge CSR (src, dst)   graph_utils.py:107, deepinteract_utils.py:442-443
  *   di_geo_feats    GeometricProteinFeatures('full') + edge/node feature assembly
@@ -434,6 +436,75 @@ int di_se_scale_add_batch(di_dtype dt, const void* x, const float* scale, const 
                           int32_t count, void* y, void* stream);
 int di_se_gate(const float* mean, const float* w1, const float* b1, const float* w2, const float* b2,
                int32_t count, int32_t channels, int32_t hidden, float* gate, void* stream);
+
+/* ---- the whole contact-head body in one call (an addition to ABI 8) -------------------------
+ * di_head_body_batch: everything between the prologue ELU(inorm_1(conv2d_1(T))) and phase2_conv
+ * (ResNet2DInputWithOptAttention.forward, deepinteract_modules.py:1234-1247) for a ragged batch of
+ * images -- the model's two dilated ResNets, 56 + 6 bottleneck blocks (ResNet.forward :1075-1095) --
+ * as one host loop over the *_batch entry points above. It adds no kernel and no arithmetic: per net
+ *   init_proj (if given):  conv 1x1 128 -> 128 (+ proj_b), ELU on its load when in_elu
+ * and per block, with x the 128-channel residual stream and `spare` the other wide buffer,
+ *   norms given:   plane_stats(x); fold(gamma1, beta1) -> conv 1x1 128 -> 64 into half0 (stats);
+ *                  fold(gamma2, beta2) -> conv 3x3 `dilation` 64 -> 64 into half1 (stats);
+ *                  fold(gamma3, beta3) -> conv 1x1 64 -> 128 into spare (stats)
+ *   no norms:      conv 1x1 (+ bias1) into half0; conv 3x3 (+ bias2) into half1; conv 1x1 into spare
+ *                  (stats); each with ELU on its load
+ *   then           fold(bias3) -> mean; di_se_gate -> gate; spare = (spare + bias3) * gate + x;
+ *                  x and spare swap
+ * -- one launch each on `stream`, whatever count is: 10 per normed block, 6 per block without norms, 1
+ * per init_proj (598 for the model). The scale / shift / mean / gate rows are rows[0 .. 3] of the
+ * arena; a 64-channel fold writes [count, 64] rows at the start of its [count, 128] room.
+ *   di_head_block  device pointers: w1 [64, 128, 1, 1], w2 [64, 64, 3, 3], w3 [128, 64, 1, 1] bf16 (the
+ *                  modules' own tensors, as di_head_conv takes them); gamma / beta 1 .. 3 fp32 [128],
+ *                  [64], [64], all six given or all six NULL; bias1, bias2 [64] fp32 (nullable; read
+ *                  only without norms: in front of a norm a bias cancels), bias3 [128] fp32 (nullable);
+ *                  the SE block's w1 [8, 128], b1 [8], w2 [128, 8], b2 [128] fp32; eps of the three
+ *                  norms; dilation 1 .. 8 of w2.
+ *   di_head_net    proj_w [128, 128, 1, 1] bf16 (NULL: no initial projection) and proj_b [128] fp32
+ *                  (nullable); blocks: HOST array [num_blocks], num_blocks >= 1; in_elu: the ELU in
+ *                  front of this net, applied by init_proj's load (so it needs proj_w).
+ *   di_head_arena  the batch's buffers: wide0 (holds the input), wide1 [128 * pixels] and half0, half1
+ *                  [64 * pixels] bf16, 16-B aligned, all different; stats (8-B aligned, stats_bytes of
+ *                  di_head_batch_layout); rows fp32 [4][count][128]; items / items_dev / count as above.
+ * nets: HOST array [num_nets] run in order. *result (host): 0 when wide0 holds the output, 1 for wide1.
+ * Same kernels on the same geometry as a caller issuing the launches itself: the same bits.
+ * Asynchronous: no allocation, no synchronisation, no graph capture; every refusal comes before the
+ * first launch, and the first launch error (hipGetLastError after each) is returned as it is.
+ * di_head_body_batch_check: the same validation on the host, without a launch. DI_EINVAL: dt other than
+ * DI_BF16, NULL nets / arena / result, num_nets or num_blocks < 1, a NULL weight or SE vector, norms
+ * partly given, in_elu without proj_w, eps < 0 or NaN, dilation outside 1 .. 8, a NULL, misaligned or
+ * repeated arena buffer, or a table the *_batch calls refuse; DI_ERANGE as they return it.
+ *
+ * di_head_logits_batch: phase2_conv(ELU(x)) (:1241, 1247) for every item of a packed 128-channel bf16
+ * buffer in one launch (the one kernel this section adds): per pixel a_c = bf16(ELU(x_c)), ELU in fp32
+ * as di_head_conv's; y_o = bf16(sum over c of w[o][c] * a_c + b[o]) for o = 0, 1, the sum in fp32 in
+ * channel order by fused multiply-adds from 0, one rounding (RNE) at the store. weight [2, 128] fp32
+ * row-major (the 1x1 kernel's values), bias [2] fp32 (nullable). x 16-B aligned. y: packed [2 * pixels]
+ * bf16, item i a contiguous [2, h, w] image at element offset 2 * px_off_i, any 2-byte alignment (what
+ * di_contact_rank takes); y must not alias x. Errors as the *_batch calls. */
+typedef struct {
+  const void* w1; const void* w2; const void* w3;
+  const float* gamma1; const float* beta1; const float* gamma2; const float* beta2;
+  const float* gamma3; const float* beta3;
+  const float* bias1; const float* bias2; const float* bias3;
+  const float* se_w1; const float* se_b1; const float* se_w2; const float* se_b2;
+  float eps; int32_t dilation;
+} di_head_block;
+typedef struct {
+  const void* proj_w; const float* proj_b; const di_head_block* blocks;
+  int32_t num_blocks, in_elu;
+} di_head_net;
+typedef struct {
+  void* wide0; void* wide1; void* half0; void* half1; void* stats; float* rows;
+  const di_head_item* items; const di_head_item* items_dev;
+  int32_t count;
+} di_head_arena;
+int di_head_body_batch(di_dtype dt, const di_head_net* nets, int32_t num_nets, const di_head_arena* arena,
+                       int32_t* result, void* stream);
+int di_head_body_batch_check(di_dtype dt, const di_head_net* nets, int32_t num_nets, const di_head_arena* arena);
+int di_head_logits_batch(di_dtype dt, const void* x, const float* weight, const float* bias,
+                         const di_head_item* items, const di_head_item* items_dev, int32_t count, void* y,
+                         void* stream);
 
 /* ---- contact ranking (an addition to ABI 8) ------------------------------------------------
  * What LitGINI.test_step does with one complex's logits (deepinteract_modules.py:2018-2101; top-k
