@@ -108,7 +108,13 @@ class DiHeadArena(ctypes.Structure):
                 ("items", ctypes.c_void_p), ("items_dev", ctypes.c_void_p), ("count", ctypes.c_int32)]
 
 
-# pair-queue words (include/deepinteract_amd.h, di_pair_queue_bytes)
+class DiRegionAttnArgs(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_void_p), ("wq", ctypes.c_void_p), ("wk", ctypes.c_void_p),
+                ("scores", ctypes.c_void_p), ("v", ctypes.c_void_p), ("y", ctypes.c_void_p),
+                ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("in_elu", ctypes.c_int32)]
+
+
+# pair-queue words(include/deepinteract_amd.h, di_pair_queue_bytes)
 PQ_READY, PQ_ERROR, PQ_GAVE_UP, PQ_SBYTES, PQ_HBYTES = 0, 32, 33, 40, 42
 
 
@@ -167,6 +173,11 @@ _SIGS = {
                             ctypes.POINTER(ctypes.c_int32), _P], ctypes.c_int),
     "di_head_body_batch_check": ([_I, ctypes.POINTER(DiHeadNet), _I, ctypes.POINTER(DiHeadArena)], ctypes.c_int),
     "di_head_logits_batch": ([_I, _P, _P, _P, _P, _P, _I, _P, _P], ctypes.c_int),
+    "di_region_scores": ([_I, ctypes.POINTER(DiRegionAttnArgs), _P], ctypes.c_int),
+    "di_region_mix": ([_I, ctypes.POINTER(DiRegionAttnArgs), _P], ctypes.c_int),
+    "di_region_attn_check": ([_I, ctypes.POINTER(DiRegionAttnArgs)], ctypes.c_int),
+    "di_region_scores_batch": ([_I, ctypes.POINTER(DiRegionAttnArgs), _P, _P, _I, _P], ctypes.c_int),
+    "di_region_mix_batch": ([_I, ctypes.POINTER(DiRegionAttnArgs), _P, _P, _I, _P], ctypes.c_int),
     "di_contact_rank_work_bytes": ([ctypes.c_int64, _I], ctypes.c_int64),
     "di_contact_rank": ([_I, _P, _I, _I, _I, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
     "di_contact_auc_work_bytes": ([ctypes.c_int64, ctypes.c_int64], ctypes.c_int64),

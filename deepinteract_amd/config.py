@@ -54,6 +54,8 @@ class GeoTConfig:
     num_interact_hidden_channels: int = 128
     num_classes: int = 2
     bn_eps: float = 1e-5
+    use_interact_attention: bool = False   # --use_interact_attention: MHA2D_1 / MHA2D_2 behind the head's ResNets
+    num_interact_attention_heads: int = 4  # --num_interact_attention_heads
 
     @property
     def head_dim(self) -> int:

@@ -2,8 +2,10 @@
 specifies; opt-in, the bf16 head's convolutions run on HIP (HeadConvOps, csrc/head_conv.hip), for one complex at a
 time or for a ragged batch of complexes with one launch per pass (HeadBatch, body_batch). Module/parameter names match the reference's ``interact_module`` so reference
 state dicts load unchanged: ResNet2DInputWithOptAttention (deepinteract_modules.py:1155-1248),
-ResNet (:973-1106), SEBlock (:954-970). The optional regional attention (MHA2D) is not part
-of the default model (``use_interact_attention=False``) and is not implemented.
+ResNet (:973-1106), SEBlock (:954-970), MultiHeadRegionalAttention (:1109-1152). The optional regional
+attention (``use_interact_attention``: MHA2D_1 / MHA2D_2 behind the two ResNets) runs its scores and its
+3x3 softmax-weighted mix on HIP (HeadAttnOps, csrc/head_attn.hip) wherever the HIP norm passes run, and as
+plain torch otherwise; neither forms the reference's ninefold stretch of q, k and v.
 """
 from __future__ import annotations
 
@@ -321,6 +323,159 @@ class HeadConvOps:
         return tuple(out[k] for k in want)
 
 
+class HeadAttnOps:
+    """The head's regional attention on HIP (csrc/head_attn.hip): the per-pixel scores of a
+    [1, 128, H, W] image and the 3x3 softmax-weighted mix of its values, fp32 or bf16 storage, for one
+    image or for every image of a HeadBatch in one launch each. The value convolution is the caller's
+    (torch, or HeadConvOps.conv). No CPU fallback: constructing it without the HIP library / a GPU
+    raises."""
+
+    CHANNELS, HEADS, DK = 128, 4, 16
+
+    def __init__(self, device):
+        from . import _lib
+        if not torch.cuda.is_available():
+            raise RuntimeError("HeadAttnOps needs a ROCm GPU (no CPU fallback)")
+        self._lib = _lib
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+
+    def _dt(self, x):
+        if x.dtype == torch.float32:
+            return self._lib.DI_F32
+        if x.dtype == torch.bfloat16:
+            return self._lib.DI_BF16
+        raise TypeError(f"the regional attention takes fp32 / bf16 images, got {x.dtype}")
+
+    def _check_image(self, x):
+        if x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != self.CHANNELS or not x.is_contiguous() or not x.is_cuda:
+            raise ValueError("the regional attention takes one contiguous NCHW [1, 128, H, W] GPU image")
+
+    def _check_qk(self, wq, wk):
+        for t in (wq, wk):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != self.DK * self.CHANNELS \
+                    or t.shape[0] != self.DK or not t.is_cuda:
+                raise ValueError("wq / wk are contiguous fp32 [16, 128] GPU tensors (the 1x1 kernels' values)")
+
+    def _check_scores(self, s, px):
+        if s.dtype != torch.float32 or not s.is_contiguous() or s.numel() != self.HEADS * px or not s.is_cuda:
+            raise ValueError(f"the scores are a contiguous fp32 GPU tensor of 4 x {px} elements")
+
+    def scores(self, x, wq, wk, in_elu=False, out=None):
+        """fp32 [4, H, W] scores of x (ELU(x) with in_elu): a pixel's own q.k per head, over sqrt(16)."""
+        self._check_image(x)
+        self._check_qk(wq, wk)
+        _, _, H, W = x.shape
+        s = torch.empty(self.HEADS, H, W, dtype=torch.float32, device=x.device) if out is None else out
+        self._check_scores(s, H * W)
+        args = self._lib.DiRegionAttnArgs(x.data_ptr(), wq.data_ptr(), wk.data_ptr(), s.data_ptr(), None, None,
+                                          H, W, int(bool(in_elu)))
+        self._lib.check(self.lib.di_region_scores(self._dt(x), ctypes.byref(args), _stream()), "di_region_scores")
+        return s
+
+    def mix(self, v, scores, out=None):
+        """The softmax over each pixel's 3x3 region of scores (taps outside the image: score 0, value 0,
+        kept in the denominator) applied to v's channels of that head. out: None (a new image) or any
+        image but v -- the scores' input may be overwritten."""
+        self._check_image(v)
+        _, _, H, W = v.shape
+        self._check_scores(scores, H * W)
+        y = torch.empty_like(v) if out is None else out
+        self._check_image(y)
+        if y.dtype != v.dtype or y.shape != v.shape or y.data_ptr() == v.data_ptr():
+            raise ValueError("mix writes an image of v's shape and dtype that is not v")
+        args = self._lib.DiRegionAttnArgs(None, None, None, scores.data_ptr(), v.data_ptr(), y.data_ptr(), H, W, 0)
+        self._lib.check(self.lib.di_region_mix(self._dt(v), ctypes.byref(args), _stream()), "di_region_mix")
+        return y
+
+    # ---- the same over a HeadBatch: one launch each ----
+    @staticmethod
+    def batch_scores_buffer(hb):
+        """The batch's [4 * pixels] fp32 scores in the arena: the front of hb.half[0] (16 of its 128 B per
+        pixel), free between two ResNets."""
+        return hb.half[0].view(torch.float32)[:HeadAttnOps.HEADS * hb.pixels]
+
+    def scores_batch(self, hb, x, wq, wk, in_elu=False, out=None):
+        """scores for every image of a HeadBatch: x a packed [128 * pixels] bf16 buffer; returns the packed
+        [4 * pixels] fp32 scores (item i at 4 * px_off_i; out: None takes batch_scores_buffer)."""
+        hb.check_packed(x, self.CHANNELS)
+        self._check_qk(wq, wk)
+        s = self.batch_scores_buffer(hb) if out is None else out
+        self._check_scores(s, hb.pixels)
+        args = self._lib.DiRegionAttnArgs(x.data_ptr(), wq.data_ptr(), wk.data_ptr(), s.data_ptr(), None, None,
+                                          0, 0, int(bool(in_elu)))
+        self._lib.check(self.lib.di_region_scores_batch(self._lib.DI_BF16, ctypes.byref(args), hb.items, hb.items_ptr,
+                                                        hb.count, _stream()), "di_region_scores_batch")
+        return s
+
+    def mix_batch(self, hb, v, scores, y):
+        """mix for every image of a HeadBatch: v, y packed [128 * pixels] bf16 buffers (y is not v)."""
+        hb.check_packed(v, self.CHANNELS), hb.check_packed(y, self.CHANNELS)
+        self._check_scores(scores, hb.pixels)
+        if y.data_ptr() == v.data_ptr():
+            raise ValueError("mix_batch writes a buffer that is not v")
+        args = self._lib.DiRegionAttnArgs(None, None, None, scores.data_ptr(), v.data_ptr(), y.data_ptr(), 0, 0, 0)
+        self._lib.check(self.lib.di_region_mix_batch(self._lib.DI_BF16, ctypes.byref(args), hb.items, hb.items_ptr,
+                                                     hb.count, _stream()), "di_region_mix_batch")
+        return y
+
+
+class _StretchWeight(nn.Module):
+    """The reference's ``stretch_layer`` (a bias-free Conv3d whose fixed one-hot weight copies tap (i, j)
+    of the 3x3 region into channel 3 i + j): only its weight is kept, so that a reference state dict
+    loads unchanged, and checked on load -- the region it encodes is what forward and the kernels
+    compute."""
+
+    def __init__(self, region=3):
+        super().__init__()
+        from .weights import stretch_weight
+        self.region = region
+        self.weight = nn.Parameter(stretch_weight(region), requires_grad=False)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        from .weights import stretch_weight
+        w = state_dict.get(prefix + "weight")
+        want = stretch_weight(self.region)
+        if w is not None and tuple(w.shape) == tuple(want.shape) and \
+                not torch.equal(w.detach().to("cpu", torch.float32), want):
+            raise ValueError(f"{prefix}weight is not the reference's fixed one-hot stretch pattern: the regional "
+                             "attention hard-wires it")
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+
+class MultiHeadRegionalAttention(nn.Module):
+    """deepinteract_modules.py:1109-1152 with the head's arguments (d_k 16, d_v = in_dim, output_score=True),
+    restated without the ninefold stretch of q, k and v: a pixel's score is its own q.k per head over
+    ``temper``; the output is the softmax over the 3x3 region's scores applied to the region's values,
+    a tap outside the image counting with score 0 and value 0. Dropout is the identity (inference).
+    Plain torch, any device: the path of the CPU head, of ``head_hip_ops=False`` and of a channels-last
+    head; HeadAttnOps runs the same on HIP. Returns (out, attention scores [B * n_head, 9, H, W])."""
+
+    def __init__(self, in_dim=128, region_size=3, d_k=16, d_v=128, n_head=4):
+        super().__init__()
+        if region_size != 3:
+            raise NotImplementedError("the regional attention is built for a 3x3 region")
+        self.temper = int(d_k ** 0.5)
+        self.n_head, self.dk_per_head, self.dv_per_head = n_head, d_k // n_head, d_v // n_head
+        self.q_layer = nn.Conv2d(in_dim, d_k, 1, bias=False)
+        self.k_layer = nn.Conv2d(in_dim, d_k, 1, bias=False)
+        self.v_layer = nn.Conv2d(in_dim, d_v, 1, bias=False)
+        self.stretch_layer = _StretchWeight(region_size)
+
+    def forward(self, x):
+        B, _, H, W = x.shape
+        q, k, v = self.q_layer(x), self.k_layer(x), self.v_layer(x)
+        s = (q * k).reshape(B, self.n_head, self.dk_per_head, H, W).sum(2) / self.temper
+        sp, vp = F.pad(s, (1, 1, 1, 1)), F.pad(v, (1, 1, 1, 1))
+        taps = [(i, j) for i in range(3) for j in range(3)]
+        att = torch.softmax(torch.stack([sp[:, :, i:i + H, j:j + W] for i, j in taps], 2), 2)   # [B, n_head, 9, H, W]
+        out = None
+        for n, (i, j) in enumerate(taps):
+            term = att[:, :, n, None] * vp[:, :, i:i + H, j:j + W].reshape(B, self.n_head, self.dv_per_head, H, W)
+            out = term if out is None else out + term
+        return out.reshape(B, -1, H, W), att.reshape(B * self.n_head, 9, H, W)
+
+
 class SEBlock(nn.Module):
     def __init__(self, ch, ratio=16):
         super().__init__()
@@ -488,20 +643,29 @@ class ResNet(nn.Module):
 
 
 class ResNet2DInputWithOptAttention(nn.Module):
-    def __init__(self, num_chunks=14, init_channels=256, num_channels=128, num_classes=2):
+    def __init__(self, num_chunks=14, init_channels=256, num_channels=128, num_classes=2, use_attention=False,
+                 n_head=4):
         super().__init__()
+        if use_attention and n_head != 4:
+            raise NotImplementedError("the head's regional attention is specialised for 4 heads")
+        self.use_attention = bool(use_attention)
         self.conv2d_1 = nn.Conv2d(init_channels, num_channels, 1)
         self.inorm_1 = nn.InstanceNorm2d(num_channels, eps=1e-06, affine=True)
         self.base_resnet = ResNet(num_channels, num_chunks, "base_resnet", inorm=True, initial_projection=True)
         self.phase2_resnet = ResNet(num_channels, 1, "bin_resnet", inorm=False, initial_projection=True,
                                     extra_blocks=True)
         self.phase2_conv = nn.Conv2d(num_channels, num_classes, 1)
+        if self.use_attention:   # registered last, as the reference does (:1206-1216)
+            self.MHA2D_1 = MultiHeadRegionalAttention(num_channels, d_v=num_channels, n_head=n_head)
+            self.MHA2D_2 = MultiHeadRegionalAttention(num_channels, d_v=num_channels, n_head=n_head)
         self.ops = None
         self.cops = None
+        self.aops = None  # HeadAttnOps: the regional attention on HIP, in place with the HIP norm passes
 
     def use_hip_norm_ops(self, ops):
         """Route the InstanceNorm+ELU and SE+residual passes through HeadNormOps (or None: torch)."""
         self.ops = self.base_resnet.ops = self.phase2_resnet.ops = ops
+        self.aops = HeadAttnOps(ops.device) if ops is not None and self.use_attention else None
         return self
 
     def use_hip_convs(self, cops):
@@ -524,11 +688,55 @@ class ResNet2DInputWithOptAttention(nn.Module):
             if self.ops is None:
                 raise RuntimeError("the HIP convolutions need the HIP norm passes (use_hip_norm_ops) too")
             x = self.base_resnet._forward_hipconv(x, self.ops, self.cops)
+            if self.use_attention:
+                x = self._attention_hipconv(self.MHA2D_1, x)
             x = self.phase2_resnet._forward_hipconv(x, self.ops, self.cops, in_elu=True)
+            if self.use_attention:
+                x = self._attention_hipconv(self.MHA2D_2, x)
             return self.phase2_conv(F.elu(x))
         x = F.elu(self.base_resnet(x))
+        if self.use_attention:
+            x = F.elu(self._attention(self.MHA2D_1, x))
         x = F.elu(self.phase2_resnet(x))
+        if self.use_attention:
+            x = F.elu(self._attention(self.MHA2D_2, x))
         return self.phase2_conv(x)
+
+    def _qk(self, mha):
+        """The block's q / k weights as HeadAttnOps takes them: fp32 [16, 128] (cached copies for a bf16 head)."""
+        return (self.ops.f32(mha.q_layer.weight).view(HeadAttnOps.DK, -1),
+                self.ops.f32(mha.k_layer.weight).view(HeadAttnOps.DK, -1))
+
+    def _attention(self, mha, x):
+        """mha(x)[0] with torch convolutions: scores and mix on HIP (the value convolution on torch) where the
+        HIP norm passes are in place and x is one NCHW image on the GPU; the module's torch path otherwise
+        (the CPU, head_hip_ops=False, a channels-last head)."""
+        aops = getattr(self, "aops", None)
+        if aops is None or not x.is_cuda or not x.is_contiguous() or x.shape[0] != 1 \
+                or x.shape[1] != HeadAttnOps.CHANNELS:
+            return mha(x)[0]
+        s = aops.scores(x, *self._qk(mha))
+        v = mha.v_layer(x)
+        if not v.is_contiguous():
+            v = v.contiguous()
+        return aops.mix(v, s, out=x)   # x is this forward's own ELU output: overwritten
+
+    def _attention_hipconv(self, mha, x):
+        """The same behind a ResNet whose stored output is pre-ELU (HIP convolutions): the ELU is applied
+        as the scores and the value convolution load x; the result, pre-ELU again, overwrites x."""
+        if self.aops is None:
+            raise RuntimeError("the regional attention behind the HIP convolutions needs the HIP norm passes")
+        s = self.aops.scores(x, *self._qk(mha), in_elu=True)
+        v = self.cops.conv(x, mha.v_layer.weight, in_elu=True)
+        return self.aops.mix(v, s, out=x)
+
+    def _attention_batch(self, mha, hb, x, spare):
+        """_attention_hipconv for every image of a HeadBatch, inside its arena: the scores in the front of
+        hb.half[0] (fp32), the values in the spare wide buffer, the result back over x."""
+        s = self.aops.scores_batch(hb, x, *self._qk(mha), in_elu=True)
+        self.cops.conv_batch(hb, x, mha.v_layer.weight, y=spare, in_elu=True)
+        self.aops.mix_batch(hb, spare, s, x)
+        return x, spare
 
 
     def plan(self, check="all"):
@@ -545,7 +753,11 @@ class ResNet2DInputWithOptAttention(nn.Module):
         the list of logits. Each image's logits are the same bits whatever else the batch holds.
         native: the same launches issued from C (di_head_body_batch, called on the plan's two parts) and
         phase2_conv(ELU(x)) of all images by one HIP launch (di_head_logits_batch) instead of two torch
-        kernels per image; the logits are views of one packed buffer."""
+        kernels per image; the logits are views of one packed buffer. With the regional attention
+        (use_attention) only native=False: its two blocks run inside the arena (_attention_batch)."""
+        if native and self.use_attention:
+            raise RuntimeError("body_batch(native=True) does not run the regional attention: di_head_body_batch "
+                               "has no attention stage (use native=False)")
         if getattr(self, "cops", None) is None or self.ops is None:
             raise RuntimeError("body_batch needs the HIP convolutions and norm passes (use_hip_convs, "
                                "use_hip_norm_ops)")
@@ -563,7 +775,11 @@ class ResNet2DInputWithOptAttention(nn.Module):
             plan = self.plan()
             return plan.logits(hb, hb.wide[plan.body(hb, part=1, start=which)])
         x, spare = self.base_resnet._forward_hipconv_batch(hb, hb.wide[0], hb.wide[1], self.ops, self.cops)
+        if self.use_attention:
+            x, spare = self._attention_batch(self.MHA2D_1, hb, x, spare)
         x, spare = self.phase2_resnet._forward_hipconv_batch(hb, x, spare, self.ops, self.cops, in_elu=True)
+        if self.use_attention:
+            x, spare = self._attention_batch(self.MHA2D_2, hb, x, spare)
         return [self.phase2_conv(F.elu(hb.view(x, hb.CHANNELS, i))) for i in range(hb.count)]
 
 

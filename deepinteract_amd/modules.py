@@ -87,8 +87,20 @@ class LitGINI(nn.Module):
                  num_classes=2, max_num_graph_nodes=NODE_COUNT_LIMIT, max_num_residues=RESIDUE_COUNT_LIMIT,
                  dtype="f32", head_dtype=torch.float32, precise_head=False, fuse_head_prologue=False,
                  head_channels_last=False, head_hip_ops=True, head_convs="torch", pos_prob_threshold=0.5,
-                 head_batch=0, head_batch_pixels=2 ** 22, head_body="python", **kwargs):
+                 head_batch=0, head_batch_pixels=2 ** 22, head_body="python", use_interact_attention=False,
+                 num_interact_attention_heads=4, **kwargs):
         super().__init__()
+        # use_interact_attention / num_interact_attention_heads (the reference's --use_interact_attention,
+        # --num_interact_attention_heads): a MultiHeadRegionalAttention block behind each of the head's two
+        # ResNets (MHA2D_1, MHA2D_2), on HIP with head_hip_ops (head.HeadAttnOps) and on torch otherwise
+        use_interact_attention = bool(use_interact_attention)
+        if use_interact_attention and int(num_interact_attention_heads) != 4:
+            # q / k / v are 16- / 16- / 128-channel convolutions whatever the head count, so a checkpoint
+            # trained with another head count would load and silently compute 4-head attention
+            raise NotImplementedError("the head's regional attention is specialised for 4 heads")
+        if use_interact_attention and head_body == "native":
+            raise ValueError('head_body="native" does not run the regional attention (di_head_body_batch has no '
+                             'attention stage); use head_body="python"')
         if num_gnn_hidden_channels != 128 or num_gnn_attention_heads != 4:
             # Q/K/V are Linear(H, H) whatever the head count, so a checkpoint trained with another
             # head count would load and silently compute 4-head attention
@@ -102,7 +114,9 @@ class LitGINI(nn.Module):
                               num_gnn_attention_heads=num_gnn_attention_heads, knn=knn,
                               node_count_limit=max_num_graph_nodes,
                               num_interact_layers=num_interact_layers,
-                              num_interact_hidden_channels=num_interact_hidden_channels, num_classes=num_classes)
+                              num_interact_hidden_channels=num_interact_hidden_channels, num_classes=num_classes,
+                              use_interact_attention=use_interact_attention,
+                              num_interact_attention_heads=int(num_interact_attention_heads))
         self.dtype = dtype
         self.head_dtype = head_dtype
         # precise_head: run the head's convolutions without MIOpen's fast algorithms (Winograd /
@@ -153,7 +167,9 @@ class LitGINI(nn.Module):
         # rounded predictions and confusion counts; the reference's default)
         self.pos_prob_threshold = float(pos_prob_threshold)
         self.interact_module = ResNet2DInputWithOptAttention(num_interact_layers, 2 * num_gnn_hidden_channels,
-                                                             num_interact_hidden_channels, num_classes)
+                                                             num_interact_hidden_channels, num_classes,
+                                                             use_attention=use_interact_attention,
+                                                             n_head=int(num_interact_attention_heads))
         self._geot_sd = None     # GeoT part of the reference state dict (host copy)
         self._prologue_w = None  # fp32 host copies of conv2d_1 / inorm_1 (fused head prologue)
         self._dev_ops = None     # (device, GeoTEngine, PairTensorOp, HeadPrologueOp | None)
@@ -212,7 +228,7 @@ class LitGINI(nn.Module):
         sd, arch = read_checkpoint(checkpoint_path, safe_globals=safe_globals)
         net_prefixes = ("node_in_embedding.", "gnn_module.", "interact_module.")
         sd = type(sd)((k, v) for k, v in sd.items() if k.startswith(net_prefixes))
-        arch.update({k: v for k, v in kwargs.items() if k in arch or k.startswith("num_") or k == "knn"})
+        arch.update({k: v for k, v in kwargs.items() if k in arch or k.startswith("num_") or k in ("knn", "use_interact_attention")})
         cfg = infer_config(sd, **arch)
         problems = check_state_dict(sd, cfg)
         if strict and problems:
@@ -227,6 +243,8 @@ class LitGINI(nn.Module):
                     num_interact_layers=cfg.num_interact_layers,
                     num_interact_hidden_channels=cfg.num_interact_hidden_channels, num_classes=cfg.num_classes,
                     max_num_graph_nodes=cfg.node_count_limit,
+                    use_interact_attention=cfg.use_interact_attention,
+                    num_interact_attention_heads=cfg.num_interact_attention_heads,
                     max_num_residues=int(arch.get("max_num_residues", RESIDUE_COUNT_LIMIT)), **opts)
         if map_location is not None:
             model = model.to(map_location)

@@ -144,7 +144,23 @@ def head_keys(cfg: GeoTConfig = GeoTConfig()):
     resnet(f"{p}.base_resnet", "base_resnet", cfg.num_interact_layers, True, False)
     resnet(f"{p}.phase2_resnet", "bin_resnet", 1, False, True)
     _conv(keys, f"{p}.phase2_conv", cfg.num_classes, C, 1)
+    if cfg.use_interact_attention:  # MultiHeadRegionalAttention (:1109-1152), registered last (:1206-1216)
+        for n in ("MHA2D_1", "MHA2D_2"):
+            keys.append((f"{p}.{n}.q_layer.weight", (16, C, 1, 1), "conv_w"))
+            keys.append((f"{p}.{n}.k_layer.weight", (16, C, 1, 1), "conv_w"))
+            keys.append((f"{p}.{n}.v_layer.weight", (C, C, 1, 1), "conv_w"))
+            keys.append((f"{p}.{n}.stretch_layer.weight", (9, 1, 1, 3, 3), "stretch"))
     return keys
+
+
+def stretch_weight(region: int = 3) -> torch.Tensor:
+    """MultiHeadRegionalAttention.get_stretch_weight (:1113-1118): the fixed one-hot Conv3d weight that
+    copies tap (i, j) of the region into channel region * i + j. Not trained."""
+    w = torch.zeros(region * region, 1, 1, region, region)
+    for i in range(region):
+        for j in range(region):
+            w[region * i + j, 0, 0, i, j] = 1.0
+    return w
 
 
 def _canonical_key(key: str) -> str:
@@ -162,6 +178,8 @@ def _draw(key: str, shape, kind: str, seed: int) -> torch.Tensor:
     def u(lo, hi):
         return lo + (hi - lo) * torch.rand(shape, generator=g, dtype=torch.float64)
 
+    if kind == "stretch":
+        return stretch_weight(shape[-1])
     if kind == "lin_w":
         out_f, in_f = shape
         b = math.sqrt(6.0 / (in_f + out_f))
@@ -226,6 +244,8 @@ def reference_init_state_dict(seed: int = 0, cfg: GeoTConfig = GeoTConfig(), wit
         head = key.startswith("interact_module.")
         if kind == "bn_nbt":
             t = torch.tensor(0, dtype=torch.long)
+        elif kind == "stretch":
+            t = stretch_weight(shape[-1])
         elif kind in ("bn_w", "bn_var"):
             t = torch.ones(shape)
         elif kind in ("bn_b", "bn_mean"):
@@ -274,7 +294,8 @@ def state_dict_sha256(sd) -> str:
 # training flags) has no effect on predict.
 _ARCH_HPARAMS = ("num_node_input_feats", "num_gnn_layers", "num_gnn_hidden_channels", "num_gnn_attention_heads",
                  "knn", "num_interact_layers", "num_interact_hidden_channels", "num_classes",
-                 "max_num_graph_nodes", "max_num_residues")
+                 "max_num_graph_nodes", "max_num_residues", "use_interact_attention",
+                 "num_interact_attention_heads")
 
 
 def read_checkpoint(path, safe_globals=None):
@@ -316,6 +337,12 @@ def infer_config(sd, **overrides) -> GeoTConfig:
             kw[k] = int(overrides[k])
     if "max_num_graph_nodes" in overrides:
         kw["node_count_limit"] = int(overrides["max_num_graph_nodes"])
+    if "interact_module.MHA2D_1.q_layer.weight" in sd:
+        kw["use_interact_attention"] = True
+    if "use_interact_attention" in overrides:
+        kw["use_interact_attention"] = bool(overrides["use_interact_attention"])
+    if "num_interact_attention_heads" in overrides:
+        kw["num_interact_attention_heads"] = int(overrides["num_interact_attention_heads"])
     return GeoTConfig(**kw)
 
 

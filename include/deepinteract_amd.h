@@ -506,6 +506,50 @@ int di_head_logits_batch(di_dtype dt, const void* x, const float* weight, const 
                          const di_head_item* items, const di_head_item* items_dev, int32_t count, void* y,
                          void* stream);
 
+/* ---- the head's regional attention (an addition to ABI 8) -----------------------------------
+ * MultiHeadRegionalAttention (deepinteract_modules.py:1109-1152; MHA2D_1 / MHA2D_2 of the head with
+ * use_interact_attention, :1206-1216, :1236-1244) for one [128, h, w] NCHW image, fixed at 128
+ * channels, 4 heads of 32 channels, d_k 16 and a 3 x 3 region, without the reference's ninefold
+ * stretch of q, k and v. dt: DI_F32 or DI_BF16 storage of x, v and y.
+ *   di_region_scores  a = in_elu ? ELU(x) : x in fp32 (di_head_conv's ELU); q = wq a, k = wk a per
+ *                     pixel, fused multiply-add chains over the channels in order from 0;
+ *                     scores[hd, p] = 0.25 * sum_{j = 4 hd .. 4 hd + 3} q[j, p] k[j, p]. q, k and the
+ *                     scores are fp32 throughout. wq, wk: [16, 128] fp32 row-major (the 1x1 kernels'
+ *                     values). scores: [4, h, w] fp32. x is read once.
+ *   di_region_mix     y[c, p] = sum over the 9 taps d of e_d v[c, p + d] / sum over the 9 taps of e_d,
+ *                     e_d = exp(s_d - m), s_d = scores[c / 32, p + d], m = max over the 9 taps of s_d.
+ *                     A tap outside the image has s_d = 0 and v = 0 and stays in m and in the
+ *                     denominator (a 1 x 1 image gives v e^s / (e^s + 8)). fp32 arithmetic, taps in
+ *                     row-major order, one rounding (RNE) at the store. v must be finite (an outside
+ *                     tap is a finite stand-in times a weight of exactly 0).
+ * Pointers need their element's alignment only (h * w may be odd, so planes may start on any 2-B / 4-B
+ * boundary); with 16-B aligned pointers and h * w a multiple of 4 (scores) / 8 (mix, and w <= 2048) the
+ * kernels use 16-B accesses per lane. Planes sit at 64-bit offsets. y may alias x; y must not alias v.
+ * No atomics: two runs give the same bits. Asynchronous on `stream`, nothing allocated.
+ * di_region_scores reads x, wq, wk, in_elu and writes scores; di_region_mix reads v, scores and writes y;
+ * each ignores the other's pointers. di_region_attn_check: the validation of both on the host, without
+ * a launch. DI_EINVAL: dt other than the two, h or w < 1, a NULL pointer the call reads or writes,
+ * y == v, a pointer off its element's alignment (fp32 for wq, wk, scores). DI_ERANGE: more than
+ * 2^31 - 1 tiles of 256 pixels.
+ * The *_batch forms: every item of a di_head_item table in one launch; x, v, y are packed
+ * [128 * pixels] buffers (item i at element 128 * px_off_i), scores [4 * pixels] fp32 (item i at
+ * 4 * px_off_i), h and w of the arguments are ignored. An item gets the single call's kernel body on
+ * the single call's geometry for its own sizes and pointers: the same bits. Errors as the other
+ * *_batch calls, and any item the single call refuses. */
+typedef struct {
+  const void* x; const float* wq; const float* wk;
+  float* scores;
+  const void* v; void* y;
+  int32_t h, w, in_elu;
+} di_region_attn_args;
+int di_region_scores(di_dtype dt, const di_region_attn_args* args, void* stream);
+int di_region_mix(di_dtype dt, const di_region_attn_args* args, void* stream);
+int di_region_attn_check(di_dtype dt, const di_region_attn_args* args);
+int di_region_scores_batch(di_dtype dt, const di_region_attn_args* args, const di_head_item* items,
+                           const di_head_item* items_dev, int32_t count, void* stream);
+int di_region_mix_batch(di_dtype dt, const di_region_attn_args* args, const di_head_item* items,
+                        const di_head_item* items_dev, int32_t count, void* stream);
+
 /* ---- contact ranking (an addition to ABI 8) ------------------------------------------------
  * What LitGINI.test_step does with one complex's logits (deepinteract_modules.py:2018-2101; top-k
  * precision / recall deepinteract_utils.py:977-995), without sorting the map. logits: [1, 2, l1, l2]
