@@ -160,6 +160,8 @@ _SIGS = {
     "di_channel_mean": ([_I, _P, _I, ctypes.c_int64, _P, _P, _P, _P], ctypes.c_int),
     "di_head_conv": ([_I, ctypes.POINTER(DiHeadConvArgs), _P], ctypes.c_int),
     "di_head_conv_check": ([_I, ctypes.POINTER(DiHeadConvArgs)], ctypes.c_int),
+    "di_head_conv_f32": ([ctypes.POINTER(DiHeadConvArgs), _P], ctypes.c_int),
+    "di_head_conv_f32_check": ([ctypes.POINTER(DiHeadConvArgs)], ctypes.c_int),
     "di_head_conv_stats_bytes": ([_I, _I, _I], ctypes.c_int64),
     "di_plane_stats": ([_I, _P, _I, ctypes.c_int64, _P, _P], ctypes.c_int),
     "di_head_norm_fold": ([_P, _I, ctypes.c_int64, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P], ctypes.c_int),

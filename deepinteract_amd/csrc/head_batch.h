@@ -47,4 +47,23 @@ __device__ __forceinline__ float hc_elu(float z) {
   return z > 0.f ? z : (z > -0.25f ? p : e);
 }
 
+// v + (v of the lane a DPP pattern pairs this one with), for the reduction over a row of 16 lanes:
+// quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror in turn leave every lane of
+// the row with the row's sum (after each step the lanes of a quad / half hold one value, and the next
+// pattern pairs each lane with one of the other quad / half). Both lanes of a pair add the same two
+// numbers, so every lane gets the same bits. Called with all 64 lanes active.
+template <int CTRL>
+__device__ __forceinline__ double hc_dpp_add(double v) {
+  const uint64_t u = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, 0xf, 0xf, false);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, false);
+  return v + __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double hc_row_sum(double v) {
+  v = hc_dpp_add<0xB1>(v);
+  v = hc_dpp_add<0x4E>(v);
+  v = hc_dpp_add<0x141>(v);
+  return hc_dpp_add<0x140>(v);
+}
+
 }  // namespace di

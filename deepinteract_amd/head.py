@@ -1,6 +1,7 @@
 """Dilated-ResNet contact head — on PyTorch-ROCm (MIOpen convolutions) by default, as north_star
-specifies; opt-in, the bf16 head's convolutions run on HIP (HeadConvOps, csrc/head_conv.hip), for one complex at a
-time or for a ragged batch of complexes with one launch per pass (HeadBatch, body_batch). Module/parameter names match the reference's ``interact_module`` so reference
+specifies; opt-in, the head's convolutions run on HIP (HeadConvOps: csrc/head_conv.hip for the bf16 head,
+csrc/head_conv_f32.hip for the fp32 one), for one complex at a time or, in bf16, for a ragged batch of
+complexes with one launch per pass (HeadBatch, body_batch). Module/parameter names match the reference's ``interact_module`` so reference
 state dicts load unchanged: ResNet2DInputWithOptAttention (deepinteract_modules.py:1155-1248),
 ResNet (:973-1106), SEBlock (:954-970), MultiHeadRegionalAttention (:1109-1152). The optional regional
 attention (``use_interact_attention``: MHA2D_1 / MHA2D_2 behind the two ResNets) runs its scores and its
@@ -200,11 +201,12 @@ class HeadBatch:
 
 
 class HeadConvOps:
-    """The head's convolutions on HIP (csrc/head_conv.hip): 1x1 and dilated 3x3 on the matrix cores,
-    bf16 NCHW, with the InstanceNorm + ELU in front of a convolution applied as it loads its input
-    (``ELU(x * scale + shift)``) and the next norm's statistics left by its epilogue. One
-    [1, C, H, W] contiguous bf16 GPU image per call. No CPU fallback: constructing it without the
-    HIP library / a GPU raises."""
+    """The head's convolutions on HIP (csrc/head_conv.hip, csrc/head_conv_f32.hip): 1x1 and dilated 3x3
+    on the matrix cores, NCHW, with the InstanceNorm + ELU in front of a convolution applied as it loads
+    its input (``ELU(x * scale + shift)``) and the next norm's statistics left by its epilogue. One
+    [1, C, H, W] contiguous GPU image per call, bf16 with bf16 weights (di_head_conv) or fp32 with fp32
+    weights (di_head_conv_f32); the batch passes are bf16 only. No CPU fallback: constructing it without
+    the HIP library / a GPU raises."""
 
     def __init__(self, device):
         from . import _lib
@@ -217,14 +219,17 @@ class HeadConvOps:
 
     @staticmethod
     def _check(x):
-        if x.dim() != 4 or x.shape[0] != 1 or not x.is_contiguous() or not x.is_cuda or x.dtype != torch.bfloat16:
-            raise ValueError("head convolutions take one contiguous NCHW [1, C, H, W] bf16 GPU image")
+        if x.dim() != 4 or x.shape[0] != 1 or not x.is_contiguous() or not x.is_cuda \
+                or x.dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError("head convolutions take one contiguous NCHW [1, C, H, W] bf16 or fp32 GPU image")
 
     @staticmethod
-    def _check_params(weight=None, vectors=()):
-        """The checks conv and conv_batch share: the weight tensor (if given) and fp32 per-channel vectors."""
-        if weight is not None and (weight.dtype != torch.bfloat16 or not weight.is_contiguous() or weight.dim() != 4):
-            raise ValueError("head conv weights are the module's contiguous bf16 [Cout, Cin, k, k] tensor")
+    def _check_params(weight=None, vectors=(), dtype=torch.bfloat16):
+        """The checks conv and conv_batch share: the weight tensor (if given; of the image's dtype) and fp32
+        per-channel vectors."""
+        if weight is not None and (weight.dtype != dtype or not weight.is_contiguous() or weight.dim() != 4):
+            raise ValueError(f"head conv weights are the module's contiguous [Cout, Cin, k, k] tensor in the image's "
+                             f"dtype ({dtype})")
         for v in vectors:
             if v is not None and (v.dtype != torch.float32 or not v.is_contiguous()):
                 raise ValueError("per-channel vectors are contiguous fp32")
@@ -240,10 +245,10 @@ class HeadConvOps:
     def conv(self, x, weight, bias=None, in_scale=None, in_shift=None, in_elu=False, dilation=1, stats=False):
         """conv2d(T(x), weight, bias, padding=dilation, dilation=dilation) with
         T(x) = ELU?(x * in_scale + in_shift) per channel, zero padding after T. weight: the module's
-        [Cout, Cin, k, k] bf16 tensor; bias, in_scale, in_shift: fp32 per-channel vectors or None.
-        Returns y, or (y, stats buffer) with stats=True."""
+        [Cout, Cin, k, k] tensor in x's dtype (bf16, or fp32: di_head_conv_f32); bias, in_scale, in_shift: fp32
+        per-channel vectors or None. Returns y, or (y, stats buffer) with stats=True."""
         self._check(x)
-        self._check_params(weight, (bias, in_scale, in_shift))
+        self._check_params(weight, (bias, in_scale, in_shift), dtype=x.dtype)
         _, C, H, W = x.shape
         cout, cin, k, _ = weight.shape
         if cin != C:
@@ -253,7 +258,10 @@ class HeadConvOps:
         args = self._lib.DiHeadConvArgs(x.data_ptr(), weight.data_ptr(), _ptr(in_scale).value,
                                         _ptr(in_shift).value, _ptr(bias).value, y.data_ptr(),
                                         _ptr(st).value, C, cout, H, W, k, int(dilation), int(bool(in_elu)))
-        self._lib.check(self.lib.di_head_conv(self._lib.DI_BF16, ctypes.byref(args), _stream()), "di_head_conv")
+        if x.dtype == torch.float32:
+            self._lib.check(self.lib.di_head_conv_f32(ctypes.byref(args), _stream()), "di_head_conv_f32")
+        else:
+            self._lib.check(self.lib.di_head_conv(self._lib.DI_BF16, ctypes.byref(args), _stream()), "di_head_conv")
         return (y, st) if stats else y
 
     def plane_stats(self, x):
@@ -261,8 +269,8 @@ class HeadConvOps:
         self._check(x)
         _, C, H, W = x.shape
         st = self.stats_buffer(C, H, W, x.device)
-        self._lib.check(self.lib.di_plane_stats(self._lib.DI_BF16, _ptr(x), C, H * W, _ptr(st),
-                                                _stream()), "di_plane_stats")
+        dt = self._lib.DI_F32 if x.dtype == torch.float32 else self._lib.DI_BF16
+        self._lib.check(self.lib.di_plane_stats(dt, _ptr(x), C, H * W, _ptr(st), _stream()), "di_plane_stats")
         return st
 
     def fold(self, st, C, hw, gamma=None, beta=None, eps=0.0, bias=None, want=("scale", "shift")):
@@ -669,9 +677,9 @@ class ResNet2DInputWithOptAttention(nn.Module):
         return self
 
     def use_hip_convs(self, cops):
-        """Route the ResNets' convolutions through HeadConvOps (or None: torch / MIOpen). bf16 NCHW
-        only, and with the HIP norm passes (use_hip_norm_ops) in place. conv2d_1 and phase2_conv stay
-        on torch."""
+        """Route the ResNets' convolutions through HeadConvOps (or None: torch / MIOpen). A bf16 or an
+        fp32 NCHW head, with the HIP norm passes (use_hip_norm_ops) in place. conv2d_1 and phase2_conv
+        stay on torch."""
         self.cops = self.base_resnet.cops = self.phase2_resnet.cops = cops
         return self
 

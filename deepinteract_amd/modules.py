@@ -133,13 +133,21 @@ class LitGINI(nn.Module):
         # head_hip_ops: the head's InstanceNorm+ELU and SE-gate+residual passes on HIP
         # (head.HeadNormOps; NCHW only, so not with head_channels_last)
         self.head_hip_ops = head_hip_ops and not head_channels_last
-        # head_convs: "torch" (MIOpen) or "hip": the ResNets' 1x1 / dilated 3x3 convolutions on the
-        # matrix cores with the norm + ELU fused into their loads (head.HeadConvOps). bf16 NCHW only.
-        if head_convs not in ("torch", "hip"):
-            raise ValueError(f'head_convs must be "torch" or "hip", got {head_convs!r}')
+        # head_convs: "torch" (MIOpen), or the ResNets' 1x1 / dilated 3x3 convolutions on the matrix cores
+        # with the norm + ELU fused into their loads (head.HeadConvOps), NCHW only: "hip" for the bf16 head
+        # (di_head_conv), "hip_f32" for the fp32 one (di_head_conv_f32: fp32 storage, f32-input MFMA; one
+        # complex at a time -- the batched head and the native body are bf16 only).
+        if head_convs not in ("torch", "hip", "hip_f32"):
+            raise ValueError(f'head_convs must be "torch", "hip" or "hip_f32", got {head_convs!r}')
         if head_convs == "hip" and (head_dtype != torch.bfloat16 or not head_hip_ops or head_channels_last):
             raise ValueError('head_convs="hip" needs head_dtype=torch.bfloat16, head_hip_ops=True and no '
                              "head_channels_last")
+        if head_convs == "hip_f32" and (head_dtype != torch.float32 or not head_hip_ops or head_channels_last):
+            raise ValueError('head_convs="hip_f32" needs head_dtype=torch.float32, head_hip_ops=True and no '
+                             "head_channels_last")
+        if head_convs == "hip_f32" and (int(head_batch) > 0 or head_body == "native"):
+            raise ValueError('head_convs="hip_f32" runs one complex at a time: head_batch > 0 and '
+                             'head_body="native" are the bf16-only batch (head_convs="hip")')
         self.head_convs = head_convs
         # head_batch: N > 0 sends _forward_batch's complexes through the head's blocks in chunks of at
         # most N complexes and at most head_batch_pixels pixels (L1 * L2 summed), every head kernel
@@ -207,7 +215,7 @@ class LitGINI(nn.Module):
             pair = PairTensorOp(dev)
             pro = HeadPrologueOp(*self._prologue_w, self._prologue_eps, dev) if self.fuse_head_prologue else None
             self.interact_module.use_hip_norm_ops(HeadNormOps(dev) if self.head_hip_ops else None)
-            self.interact_module.use_hip_convs(HeadConvOps(dev) if self.head_convs == "hip" else None)
+            self.interact_module.use_hip_convs(HeadConvOps(dev) if self.head_convs in ("hip", "hip_f32") else None)
             self._dev_ops = (dev, eng, pair, pro)
         return self._dev_ops[1:]
 

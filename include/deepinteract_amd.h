@@ -377,7 +377,14 @@ int di_channel_mean(di_dtype dt, const void* x, int32_t channels, int64_t hw, co
  *   scale = gamma / sqrt(var + eps), shift = beta - mean * scale   (InstanceNorm2d as an affine map:
  *           biased variance, fp64 inside; NULL gamma / beta mean 1 / 0)
  *   mean  = mean (+ bias[c], nullable)                             (the SE squeeze, as di_channel_mean)
- * as fp32 [channels]; any of the three outputs may be NULL. hw = h * w of the image. */
+ * as fp32 [channels]; any of the three outputs may be NULL. hw = h * w of the image.
+ * di_head_conv_f32: di_head_conv with fp32 storage (x, weight, y: fp32, 4-byte aligned), the same
+ * arguments and shapes: a in fp32 with no rounding of its own (the ELU's negative branch is expm1f),
+ * the sum on the f32-input matrix instructions (a k-ordered fp32 fmaf chain), bias added to the finished
+ * sum. stats: as above, of the fp32 values as stored, the same layout and di_head_conv_stats_bytes
+ * bytes; di_plane_stats(DI_F32, ...) and di_head_norm_fold take it unchanged. No atomics.
+ * di_head_conv_f32_check: its validation on the host, without a launch: di_head_conv_check's refusals
+ * but the dtype's, with 4-byte alignment. */
 typedef struct {
   const void* x; const void* weight; const float* in_scale; const float* in_shift; const float* bias;
   void* y; void* stats;
@@ -385,6 +392,8 @@ typedef struct {
 } di_head_conv_args;
 int di_head_conv(di_dtype dt, const di_head_conv_args* args, void* stream);
 int di_head_conv_check(di_dtype dt, const di_head_conv_args* args);
+int di_head_conv_f32(const di_head_conv_args* args, void* stream);
+int di_head_conv_f32_check(const di_head_conv_args* args);
 int64_t di_head_conv_stats_bytes(int32_t cout, int32_t h, int32_t w);
 int di_plane_stats(di_dtype dt, const void* x, int32_t channels, int64_t hw, void* stats, void* stream);
 int di_head_norm_fold(const void* stats, int32_t channels, int64_t hw, const float* gamma, const float* beta,

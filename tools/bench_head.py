@@ -1,8 +1,9 @@
 """Contact-head benchmark (outside the metric): the dilated-ResNet head
 (deepinteract_modules.py:1155-1248, 14 chunks x {1,2,4,8} + phase 2) on PyTorch-ROCm / MIOpen for one
-C3 complex (input [1,256,L,L]), in five forms: fp32 / bf16 NCHW with torch's InstanceNorm / ELU / SE passes,
+C3 complex (input [1,256,L,L]), in these forms: fp32 / bf16 NCHW with torch's InstanceNorm / ELU / SE passes,
 the same with those passes on HIP (head.HeadNormOps, csrc/head_ops.hip), bf16 channels-last (NHWC), and
-bf16 NCHW with the ResNets' convolutions on HIP too (head.HeadConvOps, csrc/head_conv.hip: bf16_nchw_hipconv). Prints one JSON line: ms per complex, TFLOP/s against the head's
+bf16 / fp32 NCHW with the ResNets' convolutions on HIP too (head.HeadConvOps: csrc/head_conv.hip for
+bf16_nchw_hipconv, csrc/head_conv_f32.hip for f32_nchw_hipconv). Prints one JSON line: ms per complex, TFLOP/s against the head's
 algorithmic FLOPs (~3.49 M MAC per pixel) and the bf16 logits' max error relative
 to the fp32 logits of the same input.
 
@@ -58,7 +59,8 @@ def main():
     ref = None
     variants = (("f32_nchw", torch.float32, False, False), ("f32_nchw_hipnorm", torch.float32, False, True),
                 ("bf16_nchw", torch.bfloat16, False, False), ("bf16_nchw_hipnorm", torch.bfloat16, False, True),
-                ("bf16_nhwc", torch.bfloat16, True, False), ("bf16_nchw_hipconv", torch.bfloat16, False, True))
+                ("bf16_nhwc", torch.bfloat16, True, False), ("bf16_nchw_hipconv", torch.bfloat16, False, True),
+                ("f32_nchw_hipconv", torch.float32, False, True))
     for name, dt, cl, hip in variants:
         if a.only and name not in a.only.split(","):
             continue
