@@ -54,6 +54,10 @@ class GeoTConfig:
     num_interact_hidden_channels: int = 128
     num_classes: int = 2
     bn_eps: float = 1e-5
+    # --disable_geometric_mode: the plain Graph Transformer baseline (deepinteract_modules.py:1349-1351,
+    # :1444-1451, :584, :676, :819-821, :897-904): InitEdge and the final layer's conformation module are
+    # bias-free Linear(30, H), the intermediate layers have no conformation module
+    disable_geometric_mode: bool = False
     use_interact_attention: bool = False   # --use_interact_attention: MHA2D_1 / MHA2D_2 behind the head's ResNets
     num_interact_attention_heads: int = 4  # --num_interact_attention_heads
 

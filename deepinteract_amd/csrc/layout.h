@@ -55,6 +55,17 @@ constexpr int NL_Q = 160, NL_NBLK = 256;
 constexpr int NLV_ON = 0, NLV_F1 = 128, NLV_N_FINAL = 384;
 constexpr int NLV_Q = 384, NLV_N = 768;
 
+// ---- disable_geometric_mode (geot_plain.hip; di_plain_blob_bytes kinds 0 / 1 / 2) -------------
+// always the 16x16 fragment order, no log2-unit scaling in either dtype
+// kind 0, InitEdge: W_i with the doubled columns 0 / 1 folded, [128, 28 -> 32]; no vector
+constexpr int PI_NBLK = 8;
+// kind 1, intermediate layer: projection . BN1e, O_edge, edge FFN (hidden halves / input halves)
+constexpr int PL_P = 0, PL_OE = 32, PL_F1 = 64, PL_F2 = 128, PL_NBLK = 192;
+constexpr int PLV_P = 0, PLV_OE = 128, PLV_F1 = 256, PLV_N = 512;
+// kind 2, final layer: W_c with its columns ordered [G (28), F[:,0], F[:,1], 0, 0], projection . BN1e
+constexpr int PF_WC = 0, PF_P = 8, PF_NBLK = 40;
+constexpr int PFV_P = 0, PFV_N = 128;
+
 constexpr int POS_TABLE_ROWS = 2304;  // NODE_COUNT_LIMIT
 
 }  // namespace di

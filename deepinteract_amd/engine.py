@@ -12,6 +12,9 @@ Per batch of chains (one launch per stage covers every chain of the batch):
     di_edge_layer(final)             alpha_{L-1}
     di_node_layer(final)             h_L
 
+With GeoTConfig.disable_geometric_mode (the plain Graph Transformer baseline): di_node_embed,
+di_init_edge_plain, then per layer di_edge_layer_plain and the same node launches (csrc/geot_plain.hip).
+
 This mirrors DGLGeometricTransformer.forward (deepinteract_modules.py:1426-1466): the
 returned edge features are the last INTERMEDIATE layer's (the final layer updates nodes only).
 """
@@ -97,6 +100,10 @@ class GeoTEngine:
         if layout not in (16, 32) or layout != self.lib.di_blob_layout(3, _DI_DT[dtype]) or init_layout not in (16, 32):
             raise RuntimeError(f"unexpected blob layouts {layout} / {init_layout}")
         self.packed = PackedGeoT(state_dict, dtype, cfg, self.device, edge_layout=layout, init_layout=init_layout)
+        # disable_geometric_mode: the plain edge kernels; z_init, fuse_embed_init and resident_init below
+        # have no effect, fold_attn is refused at the forward, and a batch's nbr / node_pos / geo_ref
+        # are not used
+        self.plain = bool(cfg.disable_geometric_mode)
         self._check_blob_sizes()
         self._ws = {}
         self._ws_views = {}
@@ -126,12 +133,16 @@ class GeoTEngine:
     def _check_blob_sizes(self):
         p, dt = self.packed, _DI_DT[self.dtype]
         L = p.num_layers
-        blobs = [(0, p.embed)] + [(1, p.init)] + \
-            [(3 if li == L - 1 else 2, p.edge[li]) for li in range(L)] + \
-            [(5 if li == L - 1 else 4, p.node[li]) for li in range(L)]
-        for kind, (mat, vec) in blobs:
-            want_m = self.lib.di_blob_bytes(kind, dt, 0)
-            want_v = self.lib.di_blob_bytes(kind, dt, 1)
+        q = self.lib.di_blob_bytes
+        if self.plain:
+            qp = self.lib.di_plain_blob_bytes
+            blobs = [(q, 0, p.embed), (qp, 0, p.init)] + [(qp, 2 if li == L - 1 else 1, p.edge[li]) for li in range(L)]
+        else:
+            blobs = [(q, 0, p.embed), (q, 1, p.init)] + [(q, 3 if li == L - 1 else 2, p.edge[li]) for li in range(L)]
+        blobs += [(q, 5 if li == L - 1 else 4, p.node[li]) for li in range(L)]
+        for query, kind, (mat, vec) in blobs:
+            want_m = query(kind, dt, 0)
+            want_v = query(kind, dt, 1)
             got_m = mat.numel() * mat.element_size()
             got_v = vec.numel() * vec.element_size()
             if want_m != got_m or want_v != got_v:
@@ -193,10 +204,12 @@ class GeoTEngine:
         On the z0 path (uses_z_init) the slot's f[0] is not written: InitEdge's output lives in the
         slot's z0 and layer 0 writes f[1]. Nothing reads f[0] after a forward (the returned edge
         features are f[(L-1) % 2] with L >= 2 there)."""
+        if self.plain and self.fold_attn:
+            raise ValueError("fold_attn has no disable_geometric_mode form (di_edge_layer_plain writes alpha only)")
         lib, p, dt = self.lib, self.packed, _DI_DT[self.dtype]
         check_on(self.device, "GeoTEngine.forward", gb.src, gb.dst, gb.nbr, gb.node_f, gb.edge_f,
                  gb.node_pos, gb.in_ptr, hT_out)
-        if max(gb.nodes_per_graph) > p.pos_src.shape[0]:
+        if not self.plain and max(gb.nodes_per_graph) > p.pos_src.shape[0]:
             # InitEdge gathers positional rows node_pos < max_num_graph_nodes (nn.Embedding, :153, :210)
             raise IndexError(f"chain of {max(gb.nodes_per_graph)} residues exceeds this model's "
                              f"max_num_graph_nodes={p.pos_src.shape[0]}")
@@ -215,9 +228,16 @@ class GeoTEngine:
             fn = [None, None]
         sq, sjob = (_ptr(signal[0]), int(signal[1])) if signal is not None else (_ptr(None), -1)
         tick = _Ticker(events)
-        use_z = uses_z_init(self, gb)
+        use_z = not self.plain and uses_z_init(self, gb)
         self.z_forwards += use_z
-        if use_z:
+        if self.plain:
+            tick("node_embed")
+            _lib.check(lib.di_node_embed(g, dt, gb.node_f.shape[1], _ptr(gb.node_f), _ptr(p.embed[0]),
+                                         _ptr(p.embed[1]), _ptr(h[0]), _ptr(qkv[0]), sq, sjob, st), "di_node_embed")
+            tick("init_edge")
+            _lib.check(lib.di_init_edge_plain(g, dt, _ptr(gb.edge_f), _ptr(p.init[0]), _ptr(f[0]), st),
+                       "di_init_edge_plain")
+        elif use_z:
             tick("init_edge")
             _lib.check(lib.di_embed_init_edge_z(g, dt, gb.node_f.shape[1], _ptr(gb.node_f), _ptr(p.embed[0]),
                                                 _ptr(p.embed[1]), _ptr(h[0]), _ptr(qkv[0]), _ptr(gb.edge_f),
@@ -246,7 +266,7 @@ class GeoTEngine:
                            "di_init_edge")
         L = p.num_layers
         cur = 0
-        fold = self.fold_attn and self.dtype == "bf16"
+        fold = self.fold_attn and self.dtype == "bf16" and not self.plain
         for li in range(L):
             final = li == L - 1
             nxt = 1 - cur
@@ -268,7 +288,11 @@ class GeoTEngine:
                     f_out = nxt
                 cur = nxt
                 continue
-            if use_z and li == 0:
+            if self.plain:
+                _lib.check(lib.di_edge_layer_plain(g, dt, int(final), _ptr(gb.edge_f), _ptr(f[cur]), _ptr(qkv[cur]),
+                                                   _ptr(em), _ptr(ev), _ptr(alpha), _ptr(None if final else f[nxt]),
+                                                   st), "di_edge_layer_plain")
+            elif use_z and li == 0:
                 _lib.check(lib.di_edge_layer_z(g, dt, _ptr(gb.edge_f), _ptr(ws["z0"]), _ptr(p.init[0]), _ptr(qkv[cur]),
                                                _ptr(em), _ptr(ev), _ptr(alpha), _ptr(f[nxt]), st), "di_edge_layer_z")
             else:

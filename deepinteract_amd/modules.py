@@ -47,11 +47,12 @@ class DGLGeometricTransformer(nn.Module):
     """Drop-in for deepinteract_modules.DGLGeometricTransformer (eval-mode forward)."""
 
     def __init__(self, node_count_limit=NODE_COUNT_LIMIT, num_hidden_channels=128, num_attention_heads=4,
-                 knn=20, num_layers=4, dtype="f32", **kwargs):
+                 knn=20, num_layers=4, dtype="f32", disable_geometric_mode=False, **kwargs):
         super().__init__()
         self.cfg = GeoTConfig(num_gnn_layers=num_layers, num_gnn_hidden_channels=num_hidden_channels,
                               num_gnn_attention_heads=num_attention_heads, knn=knn,
-                              node_count_limit=node_count_limit, num_node_input_feats=num_hidden_channels)
+                              node_count_limit=node_count_limit, num_node_input_feats=num_hidden_channels,
+                              disable_geometric_mode=bool(disable_geometric_mode))
         if num_hidden_channels != 128 or num_attention_heads != 4:
             raise NotImplementedError("kernels are specialised for 128 hidden channels, 4 heads")
         if node_count_limit <= 0:
@@ -88,8 +89,10 @@ class LitGINI(nn.Module):
                  dtype="f32", head_dtype=torch.float32, precise_head=False, fuse_head_prologue=False,
                  head_channels_last=False, head_hip_ops=True, head_convs="torch", pos_prob_threshold=0.5,
                  head_batch=0, head_batch_pixels=2 ** 22, head_body="python", use_interact_attention=False,
-                 num_interact_attention_heads=4, **kwargs):
+                 num_interact_attention_heads=4, disable_geometric_mode=False, **kwargs):
         super().__init__()
+        # disable_geometric_mode (the reference's --disable_geometric_mode): the plain Graph Transformer
+        # baseline in the GeoT's place, on its own HIP edge kernels (GeoTConfig, csrc/geot_plain.hip)
         # use_interact_attention / num_interact_attention_heads (the reference's --use_interact_attention,
         # --num_interact_attention_heads): a MultiHeadRegionalAttention block behind each of the head's two
         # ResNets (MHA2D_1, MHA2D_2), on HIP with head_hip_ops (head.HeadAttnOps) and on torch otherwise
@@ -116,7 +119,8 @@ class LitGINI(nn.Module):
                               num_interact_layers=num_interact_layers,
                               num_interact_hidden_channels=num_interact_hidden_channels, num_classes=num_classes,
                               use_interact_attention=use_interact_attention,
-                              num_interact_attention_heads=int(num_interact_attention_heads))
+                              num_interact_attention_heads=int(num_interact_attention_heads),
+                              disable_geometric_mode=bool(disable_geometric_mode))
         self.dtype = dtype
         self.head_dtype = head_dtype
         # precise_head: run the head's convolutions without MIOpen's fast algorithms (Winograd /
@@ -236,7 +240,7 @@ class LitGINI(nn.Module):
         sd, arch = read_checkpoint(checkpoint_path, safe_globals=safe_globals)
         net_prefixes = ("node_in_embedding.", "gnn_module.", "interact_module.")
         sd = type(sd)((k, v) for k, v in sd.items() if k.startswith(net_prefixes))
-        arch.update({k: v for k, v in kwargs.items() if k in arch or k.startswith("num_") or k in ("knn", "use_interact_attention")})
+        arch.update({k: v for k, v in kwargs.items() if k in arch or k.startswith("num_") or k in ("knn", "use_interact_attention", "disable_geometric_mode")})
         cfg = infer_config(sd, **arch)
         problems = check_state_dict(sd, cfg)
         if strict and problems:
@@ -253,6 +257,7 @@ class LitGINI(nn.Module):
                     max_num_graph_nodes=cfg.node_count_limit,
                     use_interact_attention=cfg.use_interact_attention,
                     num_interact_attention_heads=cfg.num_interact_attention_heads,
+                    disable_geometric_mode=cfg.disable_geometric_mode,
                     max_num_residues=int(arch.get("max_num_residues", RESIDUE_COUNT_LIMIT)), **opts)
         if map_location is not None:
             model = model.to(map_location)

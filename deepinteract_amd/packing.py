@@ -38,6 +38,16 @@ BLOB_SIZES = {0: (EM_NBLK, EMV_N), 1: (IE_NBLK, IEV_N), 2: (EL_NBLK, ELV_N),
               6: (EL_NBLK_CONF, ELV_N_CONF)}
 
 
+# disable_geometric_mode (csrc/geot_plain.hip): kind 0 init, 1 intermediate layer, 2 final layer
+# (di_plain_blob_bytes); BLOB_SIZES above stays the geometric mode's seven kinds
+PI_NBLK = 8
+PL_P, PL_OE, PL_F1, PL_F2, PL_NBLK = 0, 32, 64, 128, 192
+PLV_P, PLV_OE, PLV_F1, PLV_N = 0, 128, 256, 512
+PF_WC, PF_P, PF_NBLK = 0, 8, 40
+PFV_P, PFV_N = 0, 128
+PLAIN_BLOB_SIZES = {0: (PI_NBLK, 0), 1: (PL_NBLK, PLV_N), 2: (PF_NBLK, PFV_N)}
+
+
 def _np(t):
     return t.detach().cpu().to(torch.float64).numpy()
 
@@ -369,6 +379,62 @@ def node_blob(sd, li, final, dtype):
     return bb.finish()
 
 
+# ---- disable_geometric_mode blobs (csrc/geot_plain.hip; always the 16x16 fragment order) ------------
+def plain_init_matrix(sd, p="gnn_module.0.init_edge_module"):
+    """F0 = W_i . cat(G[:, 0], G[:, 1], G) (:1444-1451) as one [128, 32] map of the 28 (padded 32) edge
+    features: columns 0 and 1 of G enter twice, so their two weight columns are added (fp64)."""
+    wi = _np(sd[f"{p}.weight"])  # [128, 30]
+    w = np.zeros((wi.shape[0], 32))
+    w[:, 0:28] = wi[:, 2:30]
+    w[:, 0] += wi[:, 0]
+    w[:, 1] += wi[:, 1]
+    return w
+
+
+def plain_final_matrix(sd, li):
+    """The final layer's W_c . cat(F[:, 0], F[:, 1], G) (:897-904, F the HIDDEN edge features) with
+    the operand reordered to [G (28), F[:, 0], F[:, 1], 0, 0]: a column permutation, no fold."""
+    wc = _np(sd[f"gnn_module.0.gt_block.{li}.conformation_module.weight"])  # [128, 30]
+    w = np.zeros((wc.shape[0], 32))
+    w[:, 0:28] = wc[:, 2:30]
+    w[:, 28:30] = wc[:, 0:2]
+    return w
+
+
+def init_blob_plain(sd, dtype):
+    bb = BlobBuilder(dtype, PI_NBLK, 0)
+    bb.put(0, plain_init_matrix(sd))
+    return bb.finish()
+
+
+def edge_blob_plain(sd, li, final, dtype):
+    """final: kind 2 (W_c + projection), else kind 1 (projection, O_edge, edge FFN). No log2-unit
+    SiLU scaling in either dtype: the kernel evaluates the plain SiLU."""
+    p = f"gnn_module.0.gt_block.{li}"
+    bb = BlobBuilder(dtype, *PLAIN_BLOB_SIZES[2 if final else 1])
+    s, t = bn_affine(sd, f"{p}.batch_norm1_edge_feats")
+    w, b = fold_bn_before(*lin(sd, f"{p}.mha_module.edge_feats_projection"), s, t)
+    if final:
+        bb.put(PF_WC, plain_final_matrix(sd, li))
+        bb.put(PF_P, w)
+        bb.putv(PFV_P, b)
+        return bb.finish()
+    bb.put(PL_P, w)
+    bb.putv(PLV_P, b)
+    w, b = lin(sd, f"{p}.O_edge_feats")
+    bb.put(PL_OE, w)
+    bb.putv(PLV_OE, b)
+    s, t = bn_affine(sd, f"{p}.batch_norm2_edge_feats")
+    w1, b1 = fold_bn_before(*lin(sd, f"{p}.edge_feats_MLP.0"), s, t)
+    bb.put(PL_F1, w1[:128])
+    bb.put(PL_F1 + 32, w1[128:])
+    bb.putv(PLV_F1, b1)
+    w2 = _np(sd[f"{p}.edge_feats_MLP.3.weight"])
+    bb.put(PL_F2, w2[:, :128])
+    bb.put(PL_F2 + 32, w2[:, 128:])
+    return bb.finish()
+
+
 # fragment order of the edge-layer and InitEdge blobs the shipped library expects (di_blob_layout(1 / 2 / 3, dtype))
 EDGE_LAYOUT_DEFAULT = {"bf16": 32, "f32": 16}
 
@@ -390,10 +456,16 @@ class PackedGeoT:
         dev = torch.device(device)
         mv = lambda pair: tuple(x.to(dev).contiguous() for x in pair)  # noqa: E731
         self.embed = mv(embed_blob(sd, dtype))
-        im, iv, ps, pd = init_blob(sd, dtype, layout=init_layout)
-        self.init = mv((im, iv))
-        self.pos_src, self.pos_dst = ps.to(dev).contiguous(), pd.to(dev).contiguous()
-        self.edge = [mv(edge_blob(sd, li, li == L - 1, dtype, cfg, layout=edge_layout)) for li in range(L)]
+        self.plain = bool(cfg.disable_geometric_mode)
+        if self.plain:  # no positional tables; the plain blobs have one (16x16) fragment order
+            self.init = mv(init_blob_plain(sd, dtype))
+            self.pos_src = self.pos_dst = None
+            self.edge = [mv(edge_blob_plain(sd, li, li == L - 1, dtype)) for li in range(L)]
+        else:
+            im, iv, ps, pd = init_blob(sd, dtype, layout=init_layout)
+            self.init = mv((im, iv))
+            self.pos_src, self.pos_dst = ps.to(dev).contiguous(), pd.to(dev).contiguous()
+            self.edge = [mv(edge_blob(sd, li, li == L - 1, dtype, cfg, layout=edge_layout)) for li in range(L)]
         self.node = [mv(node_blob(sd, li, li == L - 1, dtype)) for li in range(L)]
 
     @property

@@ -153,6 +153,9 @@ class OverlappedSchedule:
                  capacity_steps=64, jobs_per_launch=0, discard_outputs=False, tap=None, allow_gave_up=False):
         if help_every < 1 or ring < 2 * help_every:
             raise ValueError("need ring >= 2 * help_every")
+        if getattr(eng, "plain", False):
+            raise NotImplementedError("the overlapped schedule has no disable_geometric_mode form: its launch "
+                                      "sequence is the geometric engine's (run GeoTEngine.forward instead)")
         if eng.dtype == "bf16" and not eng.fuse_embed_init and eng.resident_init:
             # its 12-wave block (3 x 168 VGPRs per SIMD) does not fit on a SIMD holding a pair-stream
             # wave, and the default pair launch puts store waves on every CU: InitEdge would wait for

@@ -66,28 +66,39 @@ def _conf_keys(keys, p, cfg: GeoTConfig):
     _linear(keys, f"{p}.final_linear", H, H, True)
 
 
+PLAIN_EDGE_IN = 30  # disable_geometric_mode: pos_enc, weight, then the 28 edge features
+
+
 def geot_keys(cfg: GeoTConfig = GeoTConfig()):
     """(key, shape, kind) for node_in_embedding + gnn_module.0 (DGLGeometricTransformer)."""
     H = cfg.num_gnn_hidden_channels
     keys = []
     _linear(keys, "node_in_embedding", H, cfg.num_node_input_feats, False)
     ie = "gnn_module.0.init_edge_module"
-    keys.append((f"{ie}.node_embedding.weight", (cfg.node_count_limit, H), "emb"))
-    for suffix in ("0", "1"):
-        _linear(keys, f"{ie}.edge_messages_linear_{suffix}", H, 2, False)
-        _linear(keys, f"{ie}.dist_linear_{suffix}", H, NUM_RBF, False)
-        _linear(keys, f"{ie}.dir_linear_{suffix}", H, 3, False)
-        _linear(keys, f"{ie}.orient_linear_{suffix}", H, 4, False)
-        _linear(keys, f"{ie}.amide_linear_{suffix}", H, 1, False)
-        if suffix == "0":
-            _linear(keys, f"{ie}.combined_linear_0", H, 7 * H, False)
-    _linear(keys, f"{ie}.combined_linear_1", 28, H, False)
-    _linear(keys, f"{ie}.combined_linear_2", H, 28, False)
+    plain = cfg.disable_geometric_mode
+    if plain:
+        # nn.Linear(4 + 18 + 3 + 4 + 1, H, bias=False) on cat(pos_enc, weight, edata['f']) (:1349-1351, :1444-1451)
+        _linear(keys, ie, H, PLAIN_EDGE_IN, False)
+    else:
+        keys.append((f"{ie}.node_embedding.weight", (cfg.node_count_limit, H), "emb"))
+        for suffix in ("0", "1"):
+            _linear(keys, f"{ie}.edge_messages_linear_{suffix}", H, 2, False)
+            _linear(keys, f"{ie}.dist_linear_{suffix}", H, NUM_RBF, False)
+            _linear(keys, f"{ie}.dir_linear_{suffix}", H, 3, False)
+            _linear(keys, f"{ie}.orient_linear_{suffix}", H, 4, False)
+            _linear(keys, f"{ie}.amide_linear_{suffix}", H, 1, False)
+            if suffix == "0":
+                _linear(keys, f"{ie}.combined_linear_0", H, 7 * H, False)
+        _linear(keys, f"{ie}.combined_linear_1", 28, H, False)
+        _linear(keys, f"{ie}.combined_linear_2", H, 28, False)
     L = cfg.num_gnn_layers
     for li in range(L):
         p = f"gnn_module.0.gt_block.{li}"
         final = li == L - 1
-        _conf_keys(keys, f"{p}.conformation_module", cfg)
+        if not plain:
+            _conf_keys(keys, f"{p}.conformation_module", cfg)
+        elif final:  # the final layer's nn.Linear(30, H, bias=False) (:819-821); intermediate layers have none (:584)
+            _linear(keys, f"{p}.conformation_module", H, PLAIN_EDGE_IN, False)
         _bn(keys, f"{p}.batch_norm1_node_feats", H)
         _bn(keys, f"{p}.batch_norm1_edge_feats", H)
         for q in ("Q", "K", "V", "edge_feats_projection"):
@@ -295,7 +306,7 @@ def state_dict_sha256(sd) -> str:
 _ARCH_HPARAMS = ("num_node_input_feats", "num_gnn_layers", "num_gnn_hidden_channels", "num_gnn_attention_heads",
                  "knn", "num_interact_layers", "num_interact_hidden_channels", "num_classes",
                  "max_num_graph_nodes", "max_num_residues", "use_interact_attention",
-                 "num_interact_attention_heads")
+                 "num_interact_attention_heads", "disable_geometric_mode")
 
 
 def read_checkpoint(path, safe_globals=None):
@@ -343,6 +354,10 @@ def infer_config(sd, **overrides) -> GeoTConfig:
         kw["use_interact_attention"] = bool(overrides["use_interact_attention"])
     if "num_interact_attention_heads" in overrides:
         kw["num_interact_attention_heads"] = int(overrides["num_interact_attention_heads"])
+    if "gnn_module.0.init_edge_module.weight" in sd:  # the plain mode's nn.Linear in InitEdgeModule's place
+        kw["disable_geometric_mode"] = True
+    if "disable_geometric_mode" in overrides:
+        kw["disable_geometric_mode"] = bool(overrides["disable_geometric_mode"])
     return GeoTConfig(**kw)
 
 

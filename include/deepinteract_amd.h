@@ -181,6 +181,27 @@ int di_edge_layer_z(const di_graph* g, di_dtype dt, const float* edge_f, const v
                     const void* init_wmat /*kind-1 bf16 blob*/, const void* qkv, const void* wmat,
                     const float* wvec, float* alpha_out /*[Et,4]*/, void* f_out /*[Et,128]*/, void* stream);
 
+/* disable_geometric_mode (an addition to ABI 8): the edge side of the reference's plain Graph
+ * Transformer baseline (deepinteract_modules.py:1349-1351, :1444-1451, :584, :676, :819-821, :897-904);
+ * the node side is di_node_aggregate + di_node_update / di_node_layer, unchanged. The graph's nbr,
+ * node_pos and flags are not read.
+ *   di_plain_blob_bytes  bytes of the packed blobs (packing.init_blob_plain / edge_blob_plain): kind
+ *                        0 InitEdge (no vector blob: 0 bytes), 1 intermediate layer, 2 final layer;
+ *                        -1 for any other kind or a bad dtype. Always the 16x16 fragment order.
+ *   di_init_edge_plain   F0 = W_i . cat(edge_f[:,0], edge_f[:,1], edge_f), bias-free.
+ *   di_edge_layer_plain  intermediate (final_layer = 0): c = f_in; alpha_out from BN1e / projection /
+ *                        K[src] . Q[dst] as di_edge_layer; f_out = f_in + O_edge(score) + FFN(BN2e(.)).
+ *                        final: c = W_c . cat(f_in[:,0], f_in[:,1], edge_f) -- columns 0 / 1 of the HIDDEN
+ *                        edge features, as the reference computes it -- then alpha_out; f_out is not written.
+ * DI_EINVAL, before any launch: a NULL argument (f_out may be NULL on the final layer only; stream may
+ * be NULL), g->src / g->dst NULL for the layer, num_edges <= 0, a bad dtype. */
+int64_t di_plain_blob_bytes(int kind, di_dtype dtype, int vec);
+int di_init_edge_plain(const di_graph* g, di_dtype dt, const float* edge_f /*[Et,28]*/, const void* wmat,
+                       void* f_out /*[Et,128]*/, void* stream);
+int di_edge_layer_plain(const di_graph* g, di_dtype dt, int final_layer, const float* edge_f /*[Et,28]*/,
+                        const void* f_in /*[Et,128]*/, const void* qkv /*[Nt,384]*/, const void* wmat,
+                        const float* wvec, float* alpha_out /*[Et,4]*/, void* f_out /*[Et,128]*/, void* stream);
+
 /* hT_out (optional, may be NULL): also write h_out transposed, [128, Nt] (pair-tensor input).
  * bf16: DI_ERANGE when Nt * 768 or Et * 16 reaches 2^31 (the segment sums use 32-bit byte offsets;
  * split such a batch, or use di_node_aggregate + di_node_update). */
