@@ -19,7 +19,23 @@ tests/test_gpu_geot_edge_shapes.py and tests/test_gpu_modules_ragged.py on the G
 * kNN batches (``KNN_BATCHES``): synth.synthetic_chain chains as tests/test_gpu_wide_rows.py builds
   them; ``knn_host_item`` is the same chain featurised on the CPU by oracle.build_graph.
 * ``check``: gpu_common.rel_max plus the row of the worst element.
+* ``PATHS`` / ``DEFAULTS``: the engine path table of tests/test_gpu_geot_edge_shapes.py and
+  tests/test_gpu_geot_saturated.py.
+* saturating weights (``SAT_FACTORS``, ``saturating_state_dict``): the seeded state dict with, per
+  gt_block, mha_module.Q / K scaled by s_qk and mha_module.edge_feats_projection by s_p (none of them
+  has a bias), so that both attention clamps (graph_utils.py:29-32, :58-61) bind on a sizeable share
+  of the elements and head sums without the head sums turning into a step function. Calibrated layer
+  by layer on ragged300 / general with the fp64 oracle: s_qk = sqrt(5 / q85(|K.Q / sqrt(32)|)), then
+  s_p = 5 / q75(|head sum|), rounded to quarters.
+* ``mha_variant`` / ``variant64``: a restatement of oracle.mha with three switches (element clamp,
+  head-sum clamp, element clamp moved in front of the / sqrt(32)) that records how many pre-clamp
+  values lie beyond +-5, swapped in for oracle.mha while a forward runs in float64. ``MUTANTS`` are
+  the three wrong clamp placements.
+* ``bf16_sensitivity`` / ``bf16_bound``: how far the fp64 reference itself moves when every floating
+  parameter and node_f are rounded to bf16, and the bf16 bound that follows from it.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -28,6 +44,30 @@ from oracle import geot_oracle as O
 
 LAYERS = (1, 2, 3)
 TOL = {"f32": 1e-4, "bf16": 1.5e-2}  # BASELINE.json north_star; tests/test_gpu_parity.py
+
+# (dtype, path) -> engine attributes that differ from the defaults
+PATHS = {
+    ("bf16", "default"): {},
+    ("bf16", "f_form"): {"z_init": False},
+    ("bf16", "unfused_resident"): {"fuse_embed_init": False},
+    ("bf16", "unfused_staged"): {"fuse_embed_init": False, "resident_init": False},
+    ("bf16", "fused_node"): {"split_node": False},
+    ("bf16", "fold"): {"fold_attn": True},
+    ("f32", "default"): {},
+    ("f32", "unfused"): {"fuse_embed_init": False},
+    ("f32", "fused_node"): {"split_node": False},
+}
+DEFAULTS = {"z_init": True, "fuse_embed_init": True, "resident_init": True, "split_node": True, "fold_attn": False}
+
+# gt_block index -> (s_qk, s_p); an L-deep state dict takes blocks 0 .. L-1 (block L-1 is the final layer)
+SAT_FACTORS = {0: (7.75, 1.75), 1: (4.75, 0.5), 2: (3.0, 0.25)}
+# the wrong clamp placements the saturating cases are there to tell from the reference's
+MUTANTS = {"no_element_clamp": {"elem_clamp": False}, "no_sum_clamp": {"sum_clamp": False},
+           "clamp_before_scale": {"clamp_first": True}}
+TAILS = ("elem_lo", "elem_hi", "sum_lo", "sum_hi")
+TINY_KNN = ("knn7_k3", "knn11_k3")  # 84 and 132 head sums: too few for a share of them, or for the bf16 bound
+# tests/golden/make_golden_saturated.py: the reference's own LitGINI under saturating weights
+SAT_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sat_tiny.npz")
 
 # name -> (nodes, leading in-degrees, largest drawn in-degree, seed, edges). The seeds are the first
 # that give these edge counts; tests/test_geot_cases_host.py holds the conditions a new seed must keep
@@ -45,7 +85,7 @@ FEATS = ("geo_ref", "general")
 KNN_BATCHES = {"knn7_k3": ([7], 3, 21), "knn11_k3": ([11], 3, 33), "knn21_k20": ([21], 20, 420),
                "knn20_21_k20": ([20, 21], 20, 820)}
 
-_items, _sds, _refs = {}, {}, {}
+_items, _sds, _refs, _sat_sds, _sens = {}, {}, {}, {}, {}
 
 
 def _degrees(name):
@@ -184,3 +224,172 @@ def check(got, ref64, tol=None):
     if tol is not None:
         assert err <= tol, f"rel_max {err:.3e} > {tol:.1e}, worst row {row} of {ref.shape[0]}"
     return err, row
+
+
+def scale_attention(sd, factors):
+    """A copy of sd with gt_block li's mha_module.Q / K weights times factors[li][0] and its
+    edge_feats_projection weight times factors[li][1]; every other tensor shared, unchanged."""
+    out = dict(sd)
+    for li, (s_qk, s_p) in factors.items():
+        p = f"gnn_module.0.gt_block.{li}.mha_module"
+        if f"{p}.Q.weight" not in sd:
+            continue
+        assert not any(f"{p}.{m}.bias" in sd for m in ("Q", "K", "edge_feats_projection"))
+        out[f"{p}.Q.weight"], out[f"{p}.K.weight"] = sd[f"{p}.Q.weight"] * s_qk, sd[f"{p}.K.weight"] * s_qk
+        out[f"{p}.edge_feats_projection.weight"] = sd[f"{p}.edge_feats_projection.weight"] * s_p
+    return out
+
+
+def saturating_state_dict(num_layers):
+    """state_dict(num_layers) with SAT_FACTORS applied, cached."""
+    if num_layers not in _sat_sds:
+        _sat_sds[num_layers] = scale_attention(state_dict(num_layers), SAT_FACTORS)
+    return _sat_sds[num_layers]
+
+
+def mha_variant(elem_clamp=True, sum_clamp=True, clamp_first=False, tails=None):
+    """oracle.mha restated, in the dtype of its inputs, with the clamps switchable. The defaults are
+    the reference's placement, op for op what oracle.mha does. tails: a list that receives one dict
+    per call with the numbers of elements / head sums and how many of the values the REFERENCE would
+    clamp (K.Q / sqrt(32) per element; the head sum as this variant computes it) lie below -5 / above 5."""
+    def mha(sd, p, g, node, edge, update_edge_feats):
+        src, dst, N = g["src"], g["dst"], g["num_nodes"]
+        Q = O._lin(node, sd, f"{p}.Q").view(-1, O.HEADS, O.DH)
+        K = O._lin(node, sd, f"{p}.K").view(-1, O.HEADS, O.DH)
+        V = O._lin(node, sd, f"{p}.V").view(-1, O.HEADS, O.DH)
+        P = O._lin(edge, sd, f"{p}.edge_feats_projection").view(-1, O.HEADS, O.DH)
+        score = K[src] * Q[dst]
+        pre = score / np.sqrt(O.DH)
+        if clamp_first:
+            score = score.clamp(-5.0, 5.0) / np.sqrt(O.DH)
+        else:
+            score = pre.clamp(-5.0, 5.0) if elem_clamp else pre
+        score = score * P
+        e_out = score if update_edge_feats else None
+        total = score.sum(-1, keepdim=True)
+        if tails is not None:
+            tails.append({"layer": p, "elems": pre.numel(), "sums": total.numel(),
+                          "elem_lo": int((pre < -5).sum()), "elem_hi": int((pre > 5).sum()),
+                          "sum_lo": int((total < -5).sum()), "sum_hi": int((total > 5).sum())})
+        score = torch.exp(total.clamp(-5.0, 5.0) if sum_clamp else total)
+        wV = torch.zeros(N, O.HEADS, O.DH).index_add_(0, dst, V[src] * score)
+        z = torch.zeros(N, O.HEADS, 1).index_add_(0, dst, score)
+        h = wV / (z + torch.full_like(z, 1e-6))
+        return h, e_out
+    return mha
+
+
+def tail_fractions(t):
+    """The four tail fractions of one mha_variant record, in TAILS' order."""
+    return tuple(t[k] / t["elems" if k.startswith("elem") else "sums"] for k in TAILS)
+
+
+def variant64(forward, sd, item, num_layers, **switches):
+    """forward (oracle.geot_forward, plain_cases.plain_forward) in float64 with mha_variant(**switches)
+    in oracle.mha's place (restored afterwards) -> (node, edge, [tail record per layer]), and the
+    forward's intermediates as a fourth with return_intermediates=True. fp32=True: in float32 instead."""
+    return_intermediates, fp32 = switches.pop("return_intermediates", False), switches.pop("fp32", False)
+    tails, prev = [], O.mha
+    O.mha = mha_variant(tails=tails, **switches)
+    try:
+        if fp32:
+            with torch.no_grad():
+                node, edge, inter = forward(sd, item, num_layers, True)
+        else:
+            node, edge, inter = in_fp64(forward, to64(sd), to64(item), num_layers, True)
+    finally:
+        O.mha = prev
+    assert len(tails) == num_layers
+    out = (node.numpy(), edge.numpy(), tails)
+    return out + ({k: v.numpy() for k, v in inter.items()},) if return_intermediates else out
+
+
+def bf16_sensitivity(sd, item, num_layers, key=None, forward=None):
+    """(node, edge) rel_max of the float64 forward with every floating parameter and node_f rounded to
+    bf16 against the unrounded float64 run: how far the reference itself moves under the rounding a
+    bf16 engine starts from. Cached per (key, num_layers) when a key is given."""
+    if key is not None and (key, num_layers) in _sens:
+        return _sens[key, num_layers]
+    forward = forward or O.geot_forward
+    # bf16 keeps 8 significant bits: round-to-nearest-even of every value, the cast the engines start from
+    rnd = lambda t: t.bfloat16().to(t.dtype) if torch.is_tensor(t) and t.is_floating_point() else t  # noqa: E731
+    exact = in_fp64(forward, to64(sd), to64(item), num_layers)
+    moved = in_fp64(forward, to64({k: rnd(v) for k, v in sd.items()}), to64(dict(item, node_f=rnd(item["node_f"]))),
+                    num_layers)
+    out = tuple(rel_max(m.numpy(), x.numpy()) for m, x in zip(moved, exact))
+    if key is not None:
+        _sens[key, num_layers] = out
+    return out
+
+
+def bf16_bound(sens_saturating, sens_seeded):
+    """The project's bf16 budget scaled by how much more the reference moves under bf16 rounding with
+    the saturating weights than with the seeded ones; never below the budget itself."""
+    return TOL["bf16"] * max(1.0, sens_saturating / sens_seeded)
+
+
+def sat_bounds(dtype, sens_saturating=None, sens_seeded=None):
+    """(node bound, edge bound) of one chain under saturating weights: fp32 the project's 1e-4, bf16
+    bf16_bound of that chain's two (node, edge) sensitivities."""
+    if dtype == "f32":
+        return TOL["f32"], TOL["f32"]
+    return tuple(bf16_bound(a, b) for a, b in zip(sens_saturating, sens_seeded))
+
+
+def check_tail_window(name, tails):
+    """Every layer's four tails hold 1 % .. 40 % of their elements; for the tiny kNN chains, at least
+    one element each."""
+    for t in tails:
+        for k, frac in zip(TAILS, tail_fractions(t)):
+            if name in TINY_KNN:
+                assert t[k] >= 1, (name, t["layer"], k, t)
+            else:
+                assert 0.01 <= frac <= 0.40, (name, t["layer"], k, frac, t)
+
+
+def mutant_errors(forward, sd, item, num_layers, ref):
+    """mutant name -> (node, edge) rel_max of the mutant's float64 run against ref = (node, edge)."""
+    out = {}
+    for m, switches in MUTANTS.items():
+        node, edge, _ = variant64(forward, sd, item, num_layers, **switches)
+        out[m] = (rel_max(node, ref[0]), rel_max(edge, ref[1]))
+    return out
+
+
+def check_decisive(name, errors, bf16_bounds):
+    """Each mutant misses the reference by more than twice the GPU bound on the node or the edge
+    output: in both dtypes, in fp32 alone for the tiny kNN chains."""
+    for m, (en, ee) in errors.items():
+        for dtype in ("f32",) if name in TINY_KNN else ("f32", "bf16"):
+            bn, be = sat_bounds("f32") if dtype == "f32" else bf16_bounds
+            assert en > 2 * bn or ee > 2 * be, (name, m, dtype, (en, ee), (bn, be))
+
+
+def fixture_item(z, tag):
+    """Chain g1 / g2 of a fixture as a from_arrays / oracle item."""
+    t = lambda name, dt: torch.as_tensor(z[f"{tag}_{name}"].astype(dt))  # noqa: E731
+    return {"num_nodes": int(z[f"{tag}_node_f"].shape[0]), "src": t("src", np.int64), "dst": t("dst", np.int64),
+            "src_nbr": t("src_nbr", np.int64), "dst_nbr": t("dst_nbr", np.int64),
+            "node_f": t("node_f", np.float32), "edge_f": t("edge_f", np.float32)}
+
+
+def sat_stage_errors(z, mode, tag, node, edge, inter, colsums=True):
+    """stage -> rel_max of one chain's outputs against sat_tiny.npz's (mode "geo" / "plain"): the node
+    stages in full, the edge stages at the stored rows (the chain's last among them), whose float64
+    column sums over all rows must agree as well (colsums=False: not asserted, for a mutant)."""
+    errs = {}
+    for name, got in (("node_out", node), ("layer0_node", inter["node0"])):
+        errs[name] = rel_max(got, z[f"{mode}_{tag}_{name}"])
+    for name, got, rname in (("init_edge", inter["init_edge"], "init_edge_rows"),
+                             ("layer0_edge", inter["edge0"], "layer0_edge_rows"), ("edge_out", edge, "edge_rows")):
+        rows = z[f"{mode}_{tag}_{rname}"]
+        got = np.asarray(got, dtype=np.float64)
+        assert rows[-1] == got.shape[0] - 1
+        if colsums:
+            assert np.abs(got.sum(0) - z[f"{mode}_{tag}_{name}_colsum"]).max() <= 1e-5 * np.abs(got).sum(0).max(), name
+        errs[name] = rel_max(got[rows], z[f"{mode}_{tag}_{name}"])
+    return errs
+
+
+def sat_stage_errors_unchecked(z, mode, tag, node, edge, inter):
+    return sat_stage_errors(z, mode, tag, node, edge, inter, colsums=False)

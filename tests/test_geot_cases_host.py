@@ -13,12 +13,26 @@
   the failures a tile kernel makes: the last edge row a copy of the row before it (a clamped tail
   lane stored), the last edge row zero (a tail row not stored), the last chain's node rows shifted by
   one (a wrong node offset for the third chain of the ragged batch).
+
+And what tests/test_gpu_geot_saturated.py rests on: the same chains under geot_cases'
+saturating weights. These are conditions on the inputs; if a case breaks one, the factors or a seed
+change, never the condition:
+* geot_cases.mha_variant at the reference's setting reproduces oracle64 bit for bit;
+* in every layer each of the four clamp tails (element / head sum, below -5 / above 5) holds 1 % to
+  40 % of its values, so every clamp binds without the head sums turning into a step function (the two
+  tiny kNN chains, 84 and 132 head sums: at least one value per tail);
+* oracle32 stays within 1e-5 of oracle64 (measured <= 2.2e-6), and no reference row is small;
+* each wrong clamp placement (geot_cases.MUTANTS) misses oracle64, on the node or the edge output,
+  by more than twice the bound the GPU file applies to that chain and L: fp32 1e-4, bf16 1.5e-2 times
+  the ratio by which the reference moves more under bf16 rounding with the saturating weights than
+  with the seeded ones (the two tiny kNN chains: fp32 only).
 """
 import numpy as np
 import pytest
 import torch
 
 import geot_cases as C
+from oracle import geot_oracle as O
 
 CASES = C.host_cases()
 CHAINS = [(name, g) for name, items in CASES.items() for g in range(len(items))]
@@ -129,3 +143,67 @@ def test_check_names_the_row():
         C.check(got, ref, 1.0)
     with pytest.raises(AssertionError, match="worst row 3 of 5"):
         C.check(np.nan_to_num(got, nan=1.0), ref, 1e-4)
+
+
+_sat = {}
+
+
+def _sat_ref(name, g, L):
+    """(node, edge, tails) of the saturating case, with the restatement checked against oracle64."""
+    if (name, g, L) not in _sat:
+        sd, item = C.saturating_state_dict(L), CASES[name][g]
+        node, edge, tails = C.variant64(O.geot_forward, sd, item, L)
+        rn, re = C.oracle64(sd, item, L, key=("host-sat", name, g))
+        assert np.array_equal(node, rn) and np.array_equal(edge, re)  # the reference setting IS oracle.mha
+        _sat[name, g, L] = (rn, re, tails)
+    return _sat[name, g, L]
+
+
+def test_saturating_state_dict_scales_only_the_attention_inputs():
+    for L in C.LAYERS:
+        base, sat = C.state_dict(L), C.saturating_state_dict(L)
+        assert list(base) == list(sat)
+        changed = {k for k in base if not torch.equal(base[k], sat[k])}
+        want = {f"gnn_module.0.gt_block.{li}.mha_module.{m}.weight" for li in range(L) for m in ("Q", "K", "edge_feats_projection")}
+        assert changed == want
+        for li in range(L):
+            p = f"gnn_module.0.gt_block.{li}.mha_module"
+            assert torch.equal(sat[f"{p}.K.weight"], base[f"{p}.K.weight"] * C.SAT_FACTORS[li][0])
+            assert torch.equal(sat[f"{p}.edge_feats_projection.weight"], base[f"{p}.edge_feats_projection.weight"] * C.SAT_FACTORS[li][1])
+
+
+@pytest.mark.parametrize("L", C.LAYERS)
+@pytest.mark.parametrize("name,g", CHAINS)
+def test_saturating_tails(name, g, L):
+    tails = _sat_ref(name, g, L)[2]
+    for t in tails:
+        print(f"{name} chain {g} L={L} {t['layer']}: " + ", ".join(f"{k} {f:.3f}" for k, f in zip(C.TAILS, C.tail_fractions(t))))
+    C.check_tail_window(name, tails)
+
+
+@pytest.mark.parametrize("L", C.LAYERS)
+@pytest.mark.parametrize("name,g", CHAINS)
+def test_saturating_oracle32_and_rows(name, g, L):
+    n64, e64, _ = _sat_ref(name, g, L)
+    n32, e32 = C.oracle32(C.saturating_state_dict(L), CASES[name][g], L)
+    en, ee = C.check(n32, n64)[0], C.check(e32, e64)[0]
+    print(f"saturating {name} chain {g} L={L}: oracle32 vs oracle64 node {en:.2e} edge {ee:.2e}")
+    assert max(en, ee) <= 1e-5, (en, ee)
+    for what, ref in (("node", n64), ("edge", e64)):
+        ratio = np.abs(ref).max(axis=1) / np.abs(ref).max()
+        assert ratio.min() >= 0.1, (what, int(ratio.argmin()), float(ratio.min()))
+
+
+@pytest.mark.parametrize("L", C.LAYERS)
+@pytest.mark.parametrize("name,g", CHAINS)
+def test_saturating_mutants_are_decisive(name, g, L):
+    n64, e64, _ = _sat_ref(name, g, L)
+    item = CASES[name][g]
+    sat = C.bf16_sensitivity(C.saturating_state_dict(L), item, L, key=("host-sat", name, g))
+    seeded = C.bf16_sensitivity(C.state_dict(L), item, L, key=("host", name, g))
+    bounds = C.sat_bounds("bf16", sat, seeded)
+    errors = C.mutant_errors(O.geot_forward, C.saturating_state_dict(L), item, L, (n64, e64))
+    print(f"saturating {name} chain {g} L={L}: bf16 sensitivity saturating {sat[0]:.2e} / {sat[1]:.2e}, seeded "
+          f"{seeded[0]:.2e} / {seeded[1]:.2e}, bf16 bounds {bounds[0]:.2e} / {bounds[1]:.2e}; mutants "
+          + ", ".join(f"{m} {a:.2e} / {b:.2e}" for m, (a, b) in errors.items()))
+    C.check_decisive(name, errors, bounds)

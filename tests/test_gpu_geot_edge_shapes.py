@@ -33,19 +33,7 @@ import geot_cases as C
 
 pytestmark = pytest.mark.gpu
 
-# (dtype, path) -> engine attributes that differ from the defaults
-PATHS = {
-    ("bf16", "default"): {},
-    ("bf16", "f_form"): {"z_init": False},
-    ("bf16", "unfused_resident"): {"fuse_embed_init": False},
-    ("bf16", "unfused_staged"): {"fuse_embed_init": False, "resident_init": False},
-    ("bf16", "fused_node"): {"split_node": False},
-    ("bf16", "fold"): {"fold_attn": True},
-    ("f32", "default"): {},
-    ("f32", "unfused"): {"fuse_embed_init": False},
-    ("f32", "fused_node"): {"split_node": False},
-}
-DEFAULTS = {"z_init": True, "fuse_embed_init": True, "resident_init": True, "split_node": True, "fold_attn": False}
+PATHS, DEFAULTS = C.PATHS, C.DEFAULTS  # the path table, shared with tests/test_gpu_geot_saturated.py
 # (batch, as built?): the general-featurised ragged batch is the general path as built
 FORMS = [("ragged_geo_ref", True), ("ragged_geo_ref", False), ("ragged_general", False)] + \
         [(name, form) for name in C.KNN_BATCHES for form in (True, False)]

@@ -7,7 +7,11 @@ reference on ragged in-degrees.
   residues, k = 20);
 * di_node_aggregate vs fp64 torch on a ragged CSR (in-degrees 0..40, i.e. empty segments and
   segments spanning several 16-edge chunks): <= 1e-5 relative for fp32 V, and for bf16 V (the
-  bf16 values are exact in fp32; only the fp32 accumulation rounds).
+  bf16 values are exact in fp32; only the fp32 accumulation rounds);
+* the 1e-6 of h = wV / (z + 1e-6) where it matters: a destination whose only edge, and one whose two
+  edges, carry alpha = exp(-5) in all heads, element by element at relative 1e-5. The true factor is
+  alpha / (alpha + 1e-6) = 1 - 1.48e-4 (two edges: 1 - 7.4e-5): a missing epsilon is off by >= 7.4e-5,
+  a tenfold one by >= 6.7e-4, while fp32 division and one or two adds cost < 3e-7.
 """
 import ctypes
 
@@ -92,6 +96,54 @@ def test_aggregate_ragged_csr(dtype):
     print(f"di_node_aggregate {dtype} ragged: {err:.3e}")
     assert err < 1e-5
     assert (got[deg == 0] == 0).all()
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_aggregate_epsilon_at_the_smallest_alpha(dtype):
+    """The same ragged CSR; the in-degree-1 destination (node 1) gets alpha = exp(-5) in all heads on
+    its edge, node 5 (in-degree 2 by construction) on both of its edges. V is rounded to bf16 for both
+    dtypes, so the inputs are the same exact fp32 numbers."""
+    from deepinteract_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(7)
+    n = 300
+    deg = torch.randint(0, 41, (n,), generator=g)
+    deg[:6] = torch.tensor([0, 1, 16, 17, 40, 2])
+    in_ptr = torch.zeros(n + 1, dtype=torch.int32)
+    in_ptr[1:] = torch.cumsum(deg, 0)
+    E = int(in_ptr[-1])
+    src = torch.randint(0, n, (E,), generator=g, dtype=torch.int32)
+    alpha = torch.exp(torch.empty(E, 4).uniform_(-5, 5, generator=g))
+    rows = {1: list(range(int(in_ptr[1]), int(in_ptr[2]))), 5: list(range(int(in_ptr[5]), int(in_ptr[6])))}
+    assert [len(r) for r in rows.values()] == [1, 2]
+    a_min = torch.exp(torch.tensor(-5.0))  # fp32 exp(-5), what the edge kernels' clamp leaves at the least
+    for r in rows.values():
+        alpha[r] = a_min
+    tdt = torch.float32 if dtype == "f32" else torch.bfloat16
+    qkv = torch.randn(n, 384, generator=g).bfloat16().to(tdt)
+    # the checked rows' source V positive and away from zero: the check below is relative per element,
+    # and two addends must not cancel
+    for r in rows.values():
+        qkv[src[r].long(), 256:] = qkv[src[r].long(), 256:].float().abs().clamp_min(0.25).to(tdt)
+    dev = torch.device("cuda")
+    d_src, d_ptr, d_alpha, d_qkv = src.to(dev), in_ptr.to(dev), alpha.to(dev), qkv.to(dev)
+    out = torch.full((n, 128), float("nan"), device=dev)
+    cg = _lib.DiGraph(n, E, d_src.data_ptr(), None, None, None, d_ptr.data_ptr())
+    rc = lib.di_node_aggregate(ctypes.byref(cg), _lib.DI_F32 if dtype == "f32" else _lib.DI_BF16,
+                               d_alpha.data_ptr(), d_qkv.data_ptr(), out.data_ptr(),
+                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0
+    torch.cuda.synchronize()
+    got = out.double().cpu()
+    v = qkv[:, 256:].double()
+    for node, r in rows.items():
+        a = alpha[r].double().repeat_interleave(32, dim=1)  # [edges, 128]
+        ref = (a * v[src[r].long()]).sum(0) / (a.sum(0) + 1e-6)
+        no_eps = (a * v[src[r].long()]).sum(0) / a.sum(0)
+        assert float(((no_eps - ref) / ref).abs().min()) > 7e-5  # the epsilon is visible in every element
+        err = float(((got[node] - ref) / ref).abs().max())
+        print(f"di_node_aggregate {dtype} node {node} ({len(r)} edge(s) at exp(-5)): {err:.3e}")
+        assert err <= 1e-5, (node, err)
 
 
 @pytest.mark.parametrize("final", [False, True])

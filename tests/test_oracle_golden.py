@@ -1,9 +1,15 @@
 """Pin the CPU oracle to the reference: golden vectors come from the reference's own modules
-(tests/golden/make_golden.py). Expected: bit-exact (same fp32 op sequence on CPU)."""
+(tests/golden/make_golden.py). Expected: bit-exact (same fp32 op sequence on CPU).
+
+tests/golden/sat_tiny.npz (make_golden_saturated.py) is the reference under weights that drive both
+attention clamps: the oracle and geot_cases.mha_variant's restatement must match it as they match
+tiny.npz (< 1e-6), and each wrong clamp placement (geot_cases.MUTANTS) must miss it by 100 times that,
+which is what pins the oracle's clamp order to the reference's."""
 import numpy as np
 import pytest
 import torch
 
+import geot_cases as C
 from gpu_common import chain_arrays, chain_item, load_case, rel_max
 from deepinteract_amd.weights import seeded_state_dict, state_dict_sha256
 from oracle import geot_oracle as O
@@ -101,3 +107,37 @@ def test_packed_bf16_blob_emulation_log2_units(sd):
     assert rel_max(h, z["g1_node_out"]) < 2e-2
     assert rel_max(e, z["g1_edge_out"]) < 2e-2
 
+
+
+@pytest.mark.parametrize("tag", ["g1", "g2"])
+def test_saturated_fixture_pins_the_clamp_order(tag):
+    z = np.load(C.SAT_GOLDEN)
+    sd = C.scale_attention(seeded_state_dict(0), {li: C.SAT_FACTORS[li] for li in range(2)})
+    assert str(z["geo_weights_sha256"]) == state_dict_sha256(sd)
+    assert z["geo_factors"].tolist() == [[li, *C.SAT_FACTORS[li]] for li in range(2)]
+    it = C.fixture_item(z, tag)
+    assert it["src"].numel() in (660, 420)
+    with torch.no_grad():
+        n, e, inter = O.geot_forward(sd, it, 2, return_intermediates=True)
+    errs = C.sat_stage_errors(z, "geo", tag, n.numpy(), e.numpy(), {k: v.numpy() for k, v in inter.items()})
+    print(f"oracle32 vs saturated reference {tag}: {errs}")
+    assert max(errs.values()) < 1e-6, errs
+    # the restatement with its switches at the reference's setting: float32 equal to the oracle, float64 within the bound
+    n32, e32, tails32 = C.variant64(O.geot_forward, sd, it, 2, fp32=True)
+    assert np.array_equal(n32, n.numpy()) and np.array_equal(e32, e.numpy())
+    n64, e64, tails, inter64 = C.variant64(O.geot_forward, sd, it, 2, return_intermediates=True)
+    errs64 = C.sat_stage_errors(z, "geo", tag, n64, e64, inter64)
+    print(f"float64 restatement vs saturated reference {tag}: {errs64}")
+    assert max(errs64.values()) < 1e-6, errs64
+    # every clamp binds in both layers, on the fixture's own graphs
+    assert len(tails) == 2
+    for t in tails:
+        print(f"{tag} {t['layer']}: tail fractions {C.tail_fractions(t)}")
+        assert all(t[k] > 0 for k in C.TAILS), t
+    for m, switches in C.MUTANTS.items():
+        for fp32 in (True, False):
+            mn, me, _, minter = C.variant64(O.geot_forward, sd, it, 2, return_intermediates=True, fp32=fp32, **switches)
+            merr = C.sat_stage_errors_unchecked(z, "geo", tag, mn, me, minter)
+            worst = max(merr["node_out"], merr["layer0_node"], merr["layer0_edge"], merr["edge_out"])
+            print(f"{tag} mutant {m} ({'f32' if fp32 else 'f64'}): {merr}")
+            assert worst >= 100 * 1e-6, (m, merr)

@@ -3,7 +3,12 @@ the float64 restatement against the reference's own outputs, packing, blob sizes
 refusals, configuration inference and checkpoint loading. No GPU.
 
 The fixture tests/golden/plain_tiny.npz comes from the reference's unmodified
-LitGINI(disable_geometric_mode=True) (tests/golden/make_golden_plain.py)."""
+LitGINI(disable_geometric_mode=True) (tests/golden/make_golden_plain.py).
+
+The attention clamps: tests/golden/sat_tiny.npz's plain half is the reference under plain_cases'
+saturating weights, which plain_forward64 must match as it matches plain_tiny.npz while each wrong
+clamp placement misses it by 100 times the bound; and the conditions on the saturating inputs of
+tests/test_gpu_geot_saturated.py's plain tests, as tests/test_geot_cases_host.py states them."""
 import ctypes
 import os
 import types
@@ -12,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import geot_cases as C
 import plain_cases as P
 from blob_emulator import _unpack
 from deepinteract_amd import _lib, packing
@@ -245,3 +251,70 @@ def test_fold_attn_and_overlapped_schedule_are_refused():
     fake = types.SimpleNamespace(plain=True, dtype="bf16", fuse_embed_init=True, resident_init=False)
     with pytest.raises(NotImplementedError, match="disable_geometric_mode"):
         OverlappedSchedule(fake, [], [], [], [], [], [])
+
+
+@pytest.mark.parametrize("tag", ["g1", "g2"])
+def test_saturated_fixture_pins_the_clamp_order(tag):
+    z = np.load(C.SAT_GOLDEN)
+    sd = C.scale_attention(seeded_state_dict(P.SAT_SEED, P.plain_cfg(2)), P.block_factors(2))
+    assert str(z["plain_weights_sha256"]) == state_dict_sha256(sd)
+    assert z["plain_factors"].tolist() == [[li, *P.block_factors(2)[li]] for li in range(2)]
+    it = C.fixture_item(z, tag)
+    node, edge, tails, inter = P.variant64(sd, it, 2, return_intermediates=True)
+    n64, e64 = P.plain_forward64(sd, it, 2)
+    assert np.array_equal(node, n64) and np.array_equal(edge, e64)  # the reference setting IS oracle.mha
+    errs = C.sat_stage_errors(z, "plain", tag, node, edge, inter)
+    print(f"plain_forward64 vs saturated reference {tag}: {errs}")
+    assert max(errs.values()) < 1e-5, errs
+    for t in tails:
+        print(f"{tag} {t['layer']}: tail fractions {C.tail_fractions(t)}")
+        assert all(t[k] > 0 for k in C.TAILS), t
+    for m, switches in C.MUTANTS.items():
+        mn, me, _, minter = P.variant64(sd, it, 2, return_intermediates=True, **switches)
+        merr = C.sat_stage_errors_unchecked(z, "plain", tag, mn, me, minter)
+        print(f"{tag} mutant {m}: {merr}")
+        assert max(merr["node_out"], merr["layer0_node"], merr["layer0_edge"], merr["edge_out"]) >= 100 * 1e-5, (m, merr)
+
+
+# the chains tests/test_gpu_geot_saturated.py's plain tests run (tests/test_gpu_plain.py's batches)
+SAT_CASES = {k: v for k, v in C.host_cases().items() if k != "ragged_general"}
+SAT_CHAINS = [(name, g) for name, items in SAT_CASES.items() for g in range(len(items))]
+
+
+def test_saturating_factors_apply_per_role():
+    for L in C.LAYERS:
+        f = P.block_factors(L)
+        assert sorted(f) == list(range(L)) and f[L - 1] == P.SAT_FACTORS[L - 1][1]
+        assert all(f[li] == P.SAT_FACTORS[li][0] for li in range(L - 1))
+        base, sat = P.state_dict(L, P.SAT_SEED), P.saturating_state_dict(L)
+        changed = {k for k in base if not torch.equal(base[k], sat[k])}
+        assert changed == {f"gnn_module.0.gt_block.{li}.mha_module.{m}.weight" for li in range(L)
+                           for m, s in (("Q", f[li][0]), ("K", f[li][0]), ("edge_feats_projection", f[li][1])) if s != 1.0}
+
+
+@pytest.mark.parametrize("L", C.LAYERS)
+@pytest.mark.parametrize("name,g", SAT_CHAINS)
+def test_saturating_case_conditions(name, g, L):
+    """Tails, conditioning, rows and decisive mutants of one (chain, L), geot_cases' checkers."""
+    sd, item = P.saturating_state_dict(L), SAT_CASES[name][g]
+    node, edge, tails = P.variant64(sd, item, L)
+    n64, e64 = P.plain_forward64(sd, item, L, key=("host-sat", name, g))
+    assert np.array_equal(node, n64) and np.array_equal(edge, e64)
+    for t in tails:
+        print(f"plain {name} chain {g} L={L} {t['layer']}: " + ", ".join(f"{k} {f:.3f}" for k, f in zip(C.TAILS, C.tail_fractions(t))))
+    C.check_tail_window(name, tails)
+    with torch.no_grad():
+        n32, e32 = P.plain_forward(sd, item, L)
+    en, ee = C.check(n32.numpy(), n64)[0], C.check(e32.numpy(), e64)[0]
+    assert max(en, ee) <= 1e-5, (en, ee)
+    for what, ref in (("node", n64), ("edge", e64)):
+        ratio = np.abs(ref).max(axis=1) / np.abs(ref).max()
+        assert ratio.min() >= 0.1, (what, int(ratio.argmin()), float(ratio.min()))
+    sat = P.bf16_sensitivity(sd, item, L)
+    seeded = P.bf16_sensitivity(P.state_dict(L, P.SAT_SEED), item, L)
+    bounds = C.sat_bounds("bf16", sat, seeded)
+    errors = C.mutant_errors(P.plain_forward, sd, item, L, (n64, e64))
+    print(f"plain {name} chain {g} L={L}: fp32 vs fp64 {max(en, ee):.2e}; bf16 sensitivity saturating {sat[0]:.2e} / {sat[1]:.2e}, "
+          f"seeded {seeded[0]:.2e} / {seeded[1]:.2e}, bf16 bounds {bounds[0]:.2e} / {bounds[1]:.2e}; mutants "
+          + ", ".join(f"{m} {a:.2e} / {b:.2e}" for m, (a, b) in errors.items()))
+    C.check_decisive(name, errors, bounds)
