@@ -174,6 +174,10 @@ _SIGS = {
     "di_head_norm_fold_batch": ([_P, _I, _P, _P, _I, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P], ctypes.c_int),
     "di_se_scale_add_batch": ([_I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P], ctypes.c_int),
     "di_se_gate": ([_P, _P, _P, _P, _P, _I, _I, _I, _P, _P], ctypes.c_int),
+    "di_head_conv_f32_batch": ([ctypes.POINTER(DiHeadConvArgs), _P, _P, _I, _P], ctypes.c_int),
+    "di_head_conv_f32_batch_check": ([ctypes.POINTER(DiHeadConvArgs), _P, _P, _I], ctypes.c_int),
+    "di_plane_stats_f32_batch": ([_P, _I, _P, _P, _I, _P, _P], ctypes.c_int),
+    "di_se_scale_add_f32_batch": ([_P, _P, _P, _P, _I, _P, _P, _I, _P, _P], ctypes.c_int),
     "di_head_body_batch": ([_I, ctypes.POINTER(DiHeadNet), _I, ctypes.POINTER(DiHeadArena),
                             ctypes.POINTER(ctypes.c_int32), _P], ctypes.c_int),
     "di_head_body_batch_check": ([_I, ctypes.POINTER(DiHeadNet), _I, ctypes.POINTER(DiHeadArena)], ctypes.c_int),

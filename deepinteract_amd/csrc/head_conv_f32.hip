@@ -44,6 +44,9 @@
 // Statistics: as head_conv.hip, of the fp32 values as stored -- a thread's 4 pixels in fp32, then fp64:
 // 16 lanes by DPP row exchanges (hc_row_sum, head_batch.h), 4 waves through LDS in wave order, one
 // partial per block and channel; no atomics.
+//
+// di_head_conv_f32_batch runs the same kernel over a packed ragged batch of fp32 images in one launch, as
+// di_head_conv_batch does for bf16 (head_conv.hip; the layout and the item table: include/deepinteract_amd.h).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -81,8 +84,44 @@ constexpr int f32_blocks_per_cu(int ks, int cout, int dmax) {
 
 __device__ __forceinline__ float f32_elu(float z) { return z > 0.f ? z : expm1f(z); }
 
-template <int KS, int COUT, int DMAX>
-__global__ __launch_bounds__(F32_THREADS, f32_blocks_per_cu(KS, COUT, DMAX)) void k_head_conv_f32(HcArgsF32 a) {
+// an image's own grid from its sizes (1x1: gy = 1): what a single call launches
+template <int KS>
+__device__ __forceinline__ void f32_item_grid(const HcArgsF32& a, int& gx, int& gy) {
+  if constexpr (KS == 3) {
+    gx = (a.wd + F32_TILE - 1) / F32_TILE;
+    gy = (a.h + F32_TILE - 1) / F32_TILE;
+  } else {
+    gx = (int)((a.hw + F32_PIX - 1) / F32_PIX);
+    gy = 1;
+  }
+}
+
+// One kernel serves the single call and the batch, as k_head_conv (head_conv.hip, where the form and the
+// reason for a template parameter are written out). A single call (TABLE = false, items unused) uses `a`
+// as the host filled it, and its launch's grid is the image's own. For a batch, blockIdx.z names the
+// item: a.x, a.y, a.stats, a.in_scale and a.in_shift are the packed buffers' bases, which the block
+// rebases to its item (fp32: item i of a C-channel buffer at element C * px_off_i), h, wd, hw come from the
+// item, the x / y grid is the largest item's, and a block past its own item's tile count leaves at once
+// -- as a whole, before any barrier. The statistics then count and number the ITEM's blocks, not the
+// launch's.
+template <int KS, int COUT, int DMAX, bool TABLE>
+__global__ __launch_bounds__(F32_THREADS, f32_blocks_per_cu(KS, COUT, DMAX)) void k_head_conv_f32(
+    HcArgsF32 a, const di_head_item* __restrict__ items) {
+  if constexpr (TABLE) {
+    const int z = blockIdx.z;
+    const int64_t px = items[z].px_off;
+    a.h = items[z].h;
+    a.wd = items[z].w;
+    a.hw = (int64_t)a.h * a.wd;
+    int gx, gy;
+    f32_item_grid<KS>(a, gx, gy);
+    if ((int)blockIdx.x >= gx || (int)blockIdx.y >= gy) return;
+    a.x += (int64_t)a.cin * px;
+    a.y += (int64_t)COUT * px;
+    a.stats = a.stats ? reinterpret_cast<double*>(reinterpret_cast<char*>(a.stats) + items[z].stats_off) : nullptr;
+    a.in_scale = a.in_scale ? a.in_scale + (int64_t)z * a.cin : nullptr;
+    a.in_shift = a.in_shift ? a.in_shift + (int64_t)z * a.cin : nullptr;
+  }
   constexpr int TAPS = KS * KS;
   constexpr int NCB = COUT / 16;
   constexpr int KC = f32_kc(KS, COUT);
@@ -296,8 +335,10 @@ __global__ __launch_bounds__(F32_THREADS, f32_blocks_per_cu(KS, COUT, DMAX)) voi
     }
   if (stats) {
     __syncthreads();
-    const int64_t nblk = (int64_t)gridDim.x * gridDim.y;
-    const int64_t blk = (int64_t)by * gridDim.x + bx;
+    int gx = gridDim.x, gy = gridDim.y;  // a single call's grid is the image's
+    if constexpr (TABLE) f32_item_grid<KS>(a, gx, gy);
+    const int64_t nblk = (int64_t)gx * gy;
+    const int64_t blk = (int64_t)by * gx + bx;
     double* part = a.stats + 2;
     if (tid < COUT) {
       double s = 0.0, ss = 0.0;
@@ -337,9 +378,72 @@ static int f32_check(const di_head_conv_args* a) {
   return DI_OK;
 }
 
-template <int KS, int COUT, int DMAX>
-static void f32_launch(const HcArgsF32& k, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_head_conv_f32<KS, COUT, DMAX>), grid, dim3(F32_THREADS), 0, s, k);
+template <int KS, int COUT, int DMAX, bool TABLE>
+static void f32_launch(const HcArgsF32& k, dim3 grid, hipStream_t s, const di_head_item* items) {
+  hipLaunchKernelGGL((k_head_conv_f32<KS, COUT, DMAX, TABLE>), grid, dim3(F32_THREADS), 0, s, k, items);
+}
+
+// the kernel's arguments from the call's, for an image of h x w pixels (a batch: 0 x 0, every block
+// takes its item's)
+static HcArgsF32 f32_args(const di_head_conv_args* args, int32_t h, int32_t w) {
+  HcArgsF32 k;
+  k.x = (const float*)args->x;
+  k.w = (const float*)args->weight;
+  k.in_scale = args->in_scale;
+  k.in_shift = args->in_shift;
+  k.bias = args->bias;
+  k.y = (float*)args->y;
+  k.stats = (double*)args->stats;
+  k.hw = (int64_t)h * w;
+  k.cin = args->cin;
+  k.h = h;
+  k.wd = w;
+  k.dil = args->dilation;
+  k.in_elu = args->in_elu ? 1 : 0;
+  return k;
+}
+
+// the instantiation for (ksize, cout, dilation); items: the batch's device table (TABLE), or NULL
+template <bool TABLE>
+static void f32_dispatch(const HcArgsF32& k, int ksize, int cout, int d, dim3 grid, hipStream_t s,
+                         const di_head_item* items) {
+  const bool wide = cout == 128;
+  if (ksize == 1) {
+    if (wide) f32_launch<1, 128, 0, TABLE>(k, grid, s, items);
+    else f32_launch<1, 64, 0, TABLE>(k, grid, s, items);
+  } else if (d <= 2) {
+    if (wide) f32_launch<3, 128, 2, TABLE>(k, grid, s, items);
+    else f32_launch<3, 64, 2, TABLE>(k, grid, s, items);
+  } else if (d <= 4) {
+    if (wide) f32_launch<3, 128, 4, TABLE>(k, grid, s, items);
+    else f32_launch<3, 64, 4, TABLE>(k, grid, s, items);
+  } else {
+    if (wide) f32_launch<3, 128, 8, TABLE>(k, grid, s, items);
+    else f32_launch<3, 64, 8, TABLE>(k, grid, s, items);
+  }
+}
+
+// The batch's validation: the table, then the single call's checks on every item's own sizes. On DI_OK
+// *grid is the launch's: (the largest item's gx, the largest item's gy, count).
+static int f32_batch_check(const di_head_conv_args* args, const di_head_item* items, const di_head_item* items_dev,
+                           int32_t count, dim3* grid) {
+  if (!args) return DI_EINVAL;
+  int rc = hb_check_items(items, items_dev, count);
+  if (rc != DI_OK) return rc;
+  unsigned gx = 1, gy = 1;
+  di_head_conv_args one = *args;
+  for (int32_t i = 0; i < count; ++i) {
+    one.h = items[i].h;
+    one.w = items[i].w;
+    rc = f32_check(&one);
+    if (rc != DI_OK) return rc;
+    const unsigned ix = args->ksize == 1 ? (unsigned)f32_blocks(1, one.h, one.w) : (unsigned)((one.w + F32_TILE - 1) / F32_TILE);
+    const unsigned iy = args->ksize == 1 ? 1u : (unsigned)((one.h + F32_TILE - 1) / F32_TILE);
+    gx = ix > gx ? ix : gx;
+    gy = iy > gy ? iy : gy;
+  }
+  *grid = dim3(gx, gy, (unsigned)count);
+  return DI_OK;
 }
 
 }  // namespace di
@@ -351,38 +455,27 @@ extern "C" int di_head_conv_f32_check(const di_head_conv_args* args) { return f3
 extern "C" int di_head_conv_f32(const di_head_conv_args* args, void* stream) {
   const int rc = f32_check(args);
   if (rc != DI_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  HcArgsF32 k;
-  k.x = (const float*)args->x;
-  k.w = (const float*)args->weight;
-  k.in_scale = args->in_scale;
-  k.in_shift = args->in_shift;
-  k.bias = args->bias;
-  k.y = (float*)args->y;
-  k.stats = (double*)args->stats;
-  k.hw = (int64_t)args->h * args->w;
-  k.cin = args->cin;
-  k.h = args->h;
-  k.wd = args->w;
-  k.dil = args->dilation;
-  k.in_elu = args->in_elu ? 1 : 0;
   const dim3 grid = args->ksize == 1 ? dim3((unsigned)f32_blocks(1, args->h, args->w))
                                      : dim3((args->w + F32_TILE - 1) / F32_TILE, (args->h + F32_TILE - 1) / F32_TILE);
-  const bool wide = args->cout == 128;
-  const int d = args->dilation;
-  if (args->ksize == 1) {
-    if (wide) f32_launch<1, 128, 0>(k, grid, s);
-    else f32_launch<1, 64, 0>(k, grid, s);
-  } else if (d <= 2) {
-    if (wide) f32_launch<3, 128, 2>(k, grid, s);
-    else f32_launch<3, 64, 2>(k, grid, s);
-  } else if (d <= 4) {
-    if (wide) f32_launch<3, 128, 4>(k, grid, s);
-    else f32_launch<3, 64, 4>(k, grid, s);
-  } else {
-    if (wide) f32_launch<3, 128, 8>(k, grid, s);
-    else f32_launch<3, 64, 8>(k, grid, s);
-  }
+  f32_dispatch<false>(f32_args(args, args->h, args->w), args->ksize, args->cout, args->dilation, grid,
+                      (hipStream_t)stream, nullptr);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DI_OK : (int)e;
+}
+
+extern "C" int di_head_conv_f32_batch_check(const di_head_conv_args* args, const di_head_item* items,
+                                            const di_head_item* items_dev, int32_t count) {
+  dim3 grid;
+  return f32_batch_check(args, items, items_dev, count, &grid);
+}
+
+extern "C" int di_head_conv_f32_batch(const di_head_conv_args* args, const di_head_item* items,
+                                      const di_head_item* items_dev, int32_t count, void* stream) {
+  dim3 grid;
+  const int rc = f32_batch_check(args, items, items_dev, count, &grid);
+  if (rc != DI_OK) return rc;
+  f32_dispatch<true>(f32_args(args, 0, 0), args->ksize, args->cout, args->dilation, grid, (hipStream_t)stream,
+                     items_dev);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
 }

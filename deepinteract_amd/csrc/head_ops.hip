@@ -23,6 +23,8 @@
 //    k_se_scale_add: instantiated for a batch, a block rebases its pointers and takes hw from its item
 //    of the table; for a single call it uses its arguments as given), every image with the single call's decomposition
 //    and bits; di_se_gate: SEBlock's two linears, ReLU and sigmoid for the batch's means, in fp32.
+//    di_plane_stats_f32_batch / di_se_scale_add_f32_batch: the two dtype-bound passes for packed fp32 images
+//    (the fp32 head's batch, beside di_head_conv_f32_batch); the fold and the gate serve both dtypes.
 // The convs before an InstanceNorm run without their bias (a per-channel constant cancels in
 // the normalisation exactly), so the head does no separate bias-add passes.
 // fp32 accumulation everywhere, fp64 for the statistics; bf16 storage rounds once (RNE).
@@ -487,11 +489,11 @@ extern "C" int di_head_norm_fold(const void* stats, int32_t channels, int64_t hw
   return e == hipSuccess ? DI_OK : (int)e;
 }
 
-// the widest split any item of the batch takes (the grid's x size)
-static int ho_max_split(const di_head_item* items, int32_t count, int channels) {
+// the widest split any item of the batch takes (the grid's x size); vec: elements per 16-B vector
+static int ho_max_split(const di_head_item* items, int32_t count, int channels, int vec = 8) {
   int m = 1;
   for (int32_t i = 0; i < count; ++i) {
-    const int sp = ho_split(channels, (int64_t)items[i].h * items[i].w, 8);
+    const int sp = ho_split(channels, (int64_t)items[i].h * items[i].w, vec);
     m = sp > m ? sp : m;
   }
   return m;
@@ -534,6 +536,36 @@ extern "C" int di_se_scale_add_batch(di_dtype dt, const void* x, const float* sc
   const dim3 grid(ho_max_split(items, count, channels), channels, count);
   hipLaunchKernelGGL((k_se_scale_add<u16, true>), grid, dim3(HO_THREADS), 0, (hipStream_t)stream, (const u16*)x, scale, bias,
                      (const u16*)res, (int64_t)0, (u16*)y, channels, items_dev);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DI_OK : (int)e;
+}
+
+// The fp32 forms of the two dtype-bound batch passes: the <float, true> instantiations, a 16-B vector 4
+// elements, so items start 16-B aligned when channels is a multiple of 4. Entry points of their own: the
+// bf16 ones keep refusing DI_F32.
+extern "C" int di_plane_stats_f32_batch(const void* x, int32_t channels, const di_head_item* items,
+                                        const di_head_item* items_dev, int32_t count, void* stats, void* stream) {
+  if (!x || !stats || channels <= 0 || channels > 128) return DI_EINVAL;
+  if (!aligned16(x) || ((uintptr_t)stats & 7) != 0 || (channels & 3) != 0) return DI_EINVAL;
+  const int rc = hb_check_items(items, items_dev, count);
+  if (rc != DI_OK) return rc;
+  const dim3 grid(ho_max_split(items, count, channels, 4), channels, count);
+  hipLaunchKernelGGL((k_inorm_stats<float, true>), grid, dim3(HO_THREADS), 0, (hipStream_t)stream, (const float*)x,
+                     (int64_t)0, nullptr, (int64_t*)stats, channels, items_dev);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DI_OK : (int)e;
+}
+
+extern "C" int di_se_scale_add_f32_batch(const void* x, const float* scale, const float* bias, const void* res,
+                                         int32_t channels, const di_head_item* items, const di_head_item* items_dev,
+                                         int32_t count, void* y, void* stream) {
+  if (!x || !scale || !res || !y || channels <= 0 || channels > 65535) return DI_EINVAL;
+  if (!aligned16(x) || !aligned16(res) || !aligned16(y) || (channels & 3) != 0) return DI_EINVAL;
+  const int rc = hb_check_items(items, items_dev, count);
+  if (rc != DI_OK) return rc;
+  const dim3 grid(ho_max_split(items, count, channels, 4), channels, count);
+  hipLaunchKernelGGL((k_se_scale_add<float, true>), grid, dim3(HO_THREADS), 0, (hipStream_t)stream, (const float*)x,
+                     scale, bias, (const float*)res, (int64_t)0, (float*)y, channels, items_dev);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? DI_OK : (int)e;
 }

@@ -1,7 +1,7 @@
 """Dilated-ResNet contact head — on PyTorch-ROCm (MIOpen convolutions) by default, as north_star
 specifies; opt-in, the head's convolutions run on HIP (HeadConvOps: csrc/head_conv.hip for the bf16 head,
-csrc/head_conv_f32.hip for the fp32 one), for one complex at a time or, in bf16, for a ragged batch of
-complexes with one launch per pass (HeadBatch, body_batch). Module/parameter names match the reference's ``interact_module`` so reference
+csrc/head_conv_f32.hip for the fp32 one), for one complex at a time or for a ragged batch of
+complexes with one launch per pass (HeadBatch, body_batch; bf16 or fp32). Module/parameter names match the reference's ``interact_module`` so reference
 state dicts load unchanged: ResNet2DInputWithOptAttention (deepinteract_modules.py:1155-1248),
 ResNet (:973-1106), SEBlock (:954-970), MultiHeadRegionalAttention (:1109-1152). The optional regional
 attention (``use_interact_attention``: MHA2D_1 / MHA2D_2 behind the two ResNets) runs its scores and its
@@ -99,17 +99,24 @@ class HeadNormOps:
 
 
     def se_scale_add_batch(self, hb, x, scale, res, out=None, bias=None):
-        """se_scale_add for every image of a HeadBatch in one launch: x, res, out packed [C * pixels] bf16
-        buffers (out may be x or res; None: a new buffer), scale [count, C] fp32 rows, bias [C] shared."""
+        """se_scale_add for every image of a HeadBatch in one launch: x, res, out packed [C * pixels]
+        buffers of the batch's dtype (out may be x or res; None: a new buffer), scale [count, C] fp32 rows,
+        bias [C] shared. bf16: di_se_scale_add_batch; fp32: di_se_scale_add_f32_batch."""
         C = scale.shape[1]
         hb.check_packed(x, C), hb.check_packed(res, C)
         if scale.dtype != torch.float32 or not scale.is_contiguous() or scale.shape[0] != hb.count:
             raise ValueError("the batch's gates are contiguous fp32 [count, C] rows")
         b = self.f32(bias)
         y = torch.empty_like(x) if out is None else out
-        self._lib.check(self.lib.di_se_scale_add_batch(self._lib.DI_BF16, _ptr(x), _ptr(scale), _ptr(b), _ptr(res), C,
-                                                       hb.items, hb.items_ptr, hb.count, _ptr(y), _stream()),
-                        "di_se_scale_add_batch")
+        hb.check_packed(y, C)
+        if hb.dtype == torch.float32:
+            self._lib.check(self.lib.di_se_scale_add_f32_batch(_ptr(x), _ptr(scale), _ptr(b), _ptr(res), C, hb.items,
+                                                               hb.items_ptr, hb.count, _ptr(y), _stream()),
+                            "di_se_scale_add_f32_batch")
+        else:
+            self._lib.check(self.lib.di_se_scale_add_batch(self._lib.DI_BF16, _ptr(x), _ptr(scale), _ptr(b), _ptr(res),
+                                                           C, hb.items, hb.items_ptr, hb.count, _ptr(y), _stream()),
+                            "di_se_scale_add_batch")
         return y
 
     def se_gate(self, se, mean, out=None):
@@ -134,8 +141,9 @@ class HeadBatch:
     built once from the images' (h, w), it owns the device copy of the item table, the statistics
     buffer, the per-item fp32 rows (scale, shift, mean, gate) and the arena every layer of a forward
     works in -- two 128-channel packed buffers (the residual stream and a block's output, swapping
-    roles from block to block) and two 64-channel ones: 768 B per pixel. Nothing is allocated per layer
-    and nothing is copied to the device after construction.
+    roles from block to block) and two 64-channel ones: 768 B per pixel in bf16 (the default), 1536 B per
+    pixel with dtype=torch.float32 (the fp32 parity head). Nothing is allocated per layer and nothing is
+    copied to the device after construction.
 
     Item i of a packed [C * pixels] buffer is the contiguous NCHW image ``view(buf, C, i)``. Fill
     ``input(i)`` (a [1, 128, h, w] view of the residual stream) with ELU(inorm_1(conv2d_1(T_i))) for
@@ -143,9 +151,12 @@ class HeadBatch:
 
     CHANNELS = 128
 
-    def __init__(self, shapes, device):
+    def __init__(self, shapes, device, dtype=torch.bfloat16):
         from . import _lib
         from .ranking import _table_to_device
+        if dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError(f"a head batch holds bf16 or fp32 images, got {dtype}")
+        self.dtype = dtype
         shapes = [(int(h), int(w)) for h, w in shapes]
         self.shapes, self.count = shapes, len(shapes)
         if not 1 <= self.count <= _lib.DI_BATCH_MAX:
@@ -166,16 +177,17 @@ class HeadBatch:
         self.items_dev = _table_to_device(self.items, self.device)
         self.items_ptr = _ptr(self.items_dev)
         C = self.CHANNELS
-        bf = dict(dtype=torch.bfloat16, device=self.device)
-        self.wide = [torch.empty(C * self.pixels, **bf) for _ in range(2)]
-        self.half = [torch.empty(C // 2 * self.pixels, **bf) for _ in range(2)]
+        kw = dict(dtype=dtype, device=self.device)
+        self.wide = [torch.empty(C * self.pixels, **kw) for _ in range(2)]
+        self.half = [torch.empty(C // 2 * self.pixels, **kw) for _ in range(2)]
         self.stats = torch.empty(self.stats_bytes // 8, dtype=torch.float64, device=self.device)
         self.rows = torch.empty(4, self.count, C, dtype=torch.float32, device=self.device)
 
     def check_packed(self, buf, C):
-        if buf.dtype != torch.bfloat16 or not buf.is_contiguous() or buf.numel() != C * self.pixels \
+        if buf.dtype != self.dtype or not buf.is_contiguous() or buf.numel() != C * self.pixels \
                 or buf.device != self.device:
-            raise ValueError(f"a packed buffer of this batch holds {C} x {self.pixels} bf16 elements on {self.device}")
+            raise ValueError(f"a packed buffer of this batch holds {C} x {self.pixels} {self.dtype} elements on "
+                             f"{self.device}")
 
     def view(self, buf, C, i):
         """Item i of a packed C-channel buffer as a [1, C, h, w] view."""
@@ -185,7 +197,7 @@ class HeadBatch:
     def pack(self, images):
         """A new packed buffer holding the [1, C, h, w] images (tests and tools)."""
         C = images[0].shape[1]
-        buf = torch.empty(C * self.pixels, dtype=torch.bfloat16, device=self.device)
+        buf = torch.empty(C * self.pixels, dtype=self.dtype, device=self.device)
         for i, im in enumerate(images):
             self.view(buf, C, i).copy_(im)
         return buf
@@ -205,7 +217,8 @@ class HeadConvOps:
     on the matrix cores, NCHW, with the InstanceNorm + ELU in front of a convolution applied as it loads
     its input (``ELU(x * scale + shift)``) and the next norm's statistics left by its epilogue. One
     [1, C, H, W] contiguous GPU image per call, bf16 with bf16 weights (di_head_conv) or fp32 with fp32
-    weights (di_head_conv_f32); the batch passes are bf16 only. No CPU fallback: constructing it without
+    weights (di_head_conv_f32); the batch passes take a HeadBatch of either dtype (di_head_conv_batch /
+    di_head_conv_f32_batch, di_plane_stats_batch / di_plane_stats_f32_batch). No CPU fallback: constructing it without
     the HIP library / a GPU raises."""
 
     def __init__(self, device):
@@ -290,8 +303,9 @@ class HeadConvOps:
         """conv for every image of a HeadBatch: x a packed [Cin * pixels] buffer, y the packed output
         (None: a new buffer), in_scale / in_shift [count, Cin] fp32 rows or None, weight / bias shared.
         With stats=True the batch's statistics buffer is written (every item at its stats_off).
+        Buffers and weight in the batch's dtype: bf16 (di_head_conv_batch) or fp32 (di_head_conv_f32_batch).
         Returns y, or (y, hb.stats)."""
-        self._check_params(weight)
+        self._check_params(weight, dtype=hb.dtype)
         cout, cin, k, _ = weight.shape
         hb.check_packed(x, cin)
         for v in (in_scale, in_shift):
@@ -300,22 +314,30 @@ class HeadConvOps:
                 raise ValueError("the batch's scale / shift are contiguous fp32 [count, Cin] rows")
         self._check_params(vectors=(bias,))
         if y is None:
-            y = torch.empty(cout * hb.pixels, dtype=torch.bfloat16, device=x.device)
+            y = torch.empty(cout * hb.pixels, dtype=hb.dtype, device=x.device)
         hb.check_packed(y, cout)
         args = self._lib.DiHeadConvArgs(x.data_ptr(), weight.data_ptr(), _ptr(in_scale).value,
                                         _ptr(in_shift).value, _ptr(bias).value, y.data_ptr(),
                                         hb.stats.data_ptr() if stats else None, cin, cout, 0, 0, k, int(dilation),
                                         int(bool(in_elu)))
-        self._lib.check(self.lib.di_head_conv_batch(self._lib.DI_BF16, ctypes.byref(args), hb.items, hb.items_ptr,
-                                                    hb.count, _stream()), "di_head_conv_batch")
+        if hb.dtype == torch.float32:
+            self._lib.check(self.lib.di_head_conv_f32_batch(ctypes.byref(args), hb.items, hb.items_ptr, hb.count,
+                                                            _stream()), "di_head_conv_f32_batch")
+        else:
+            self._lib.check(self.lib.di_head_conv_batch(self._lib.DI_BF16, ctypes.byref(args), hb.items, hb.items_ptr,
+                                                        hb.count, _stream()), "di_head_conv_batch")
         return (y, hb.stats) if stats else y
 
     def plane_stats_batch(self, hb, x, C):
         """The batch's statistics buffer of a packed C-channel buffer (one read pass)."""
         hb.check_packed(x, C)
-        self._lib.check(self.lib.di_plane_stats_batch(self._lib.DI_BF16, _ptr(x), C, hb.items, hb.items_ptr,
-                                                      hb.count, _ptr(hb.stats), _stream()),
-                        "di_plane_stats_batch")
+        if hb.dtype == torch.float32:
+            self._lib.check(self.lib.di_plane_stats_f32_batch(_ptr(x), C, hb.items, hb.items_ptr, hb.count,
+                                                              _ptr(hb.stats), _stream()), "di_plane_stats_f32_batch")
+        else:
+            self._lib.check(self.lib.di_plane_stats_batch(self._lib.DI_BF16, _ptr(x), C, hb.items, hb.items_ptr,
+                                                          hb.count, _ptr(hb.stats), _stream()),
+                            "di_plane_stats_batch")
         return hb.stats
 
     def fold_batch(self, hb, st, C, gamma=None, beta=None, eps=0.0, bias=None, want=("scale", "shift"), out=None):
@@ -400,11 +422,12 @@ class HeadAttnOps:
     @staticmethod
     def batch_scores_buffer(hb):
         """The batch's [4 * pixels] fp32 scores in the arena: the front of hb.half[0] (16 of its 128 B per
-        pixel), free between two ResNets."""
-        return hb.half[0].view(torch.float32)[:HeadAttnOps.HEADS * hb.pixels]
+        pixel in bf16, of its 256 B in fp32), free between two ResNets."""
+        half = hb.half[0] if hb.dtype == torch.float32 else hb.half[0].view(torch.float32)
+        return half[:HeadAttnOps.HEADS * hb.pixels]
 
     def scores_batch(self, hb, x, wq, wk, in_elu=False, out=None):
-        """scores for every image of a HeadBatch: x a packed [128 * pixels] bf16 buffer; returns the packed
+        """scores for every image of a HeadBatch: x a packed [128 * pixels] buffer; returns the packed
         [4 * pixels] fp32 scores (item i at 4 * px_off_i; out: None takes batch_scores_buffer)."""
         hb.check_packed(x, self.CHANNELS)
         self._check_qk(wq, wk)
@@ -412,18 +435,18 @@ class HeadAttnOps:
         self._check_scores(s, hb.pixels)
         args = self._lib.DiRegionAttnArgs(x.data_ptr(), wq.data_ptr(), wk.data_ptr(), s.data_ptr(), None, None,
                                           0, 0, int(bool(in_elu)))
-        self._lib.check(self.lib.di_region_scores_batch(self._lib.DI_BF16, ctypes.byref(args), hb.items, hb.items_ptr,
+        self._lib.check(self.lib.di_region_scores_batch(self._dt(x), ctypes.byref(args), hb.items, hb.items_ptr,
                                                         hb.count, _stream()), "di_region_scores_batch")
         return s
 
     def mix_batch(self, hb, v, scores, y):
-        """mix for every image of a HeadBatch: v, y packed [128 * pixels] bf16 buffers (y is not v)."""
+        """mix for every image of a HeadBatch: v, y packed [128 * pixels] buffers (y is not v)."""
         hb.check_packed(v, self.CHANNELS), hb.check_packed(y, self.CHANNELS)
         self._check_scores(scores, hb.pixels)
         if y.data_ptr() == v.data_ptr():
             raise ValueError("mix_batch writes a buffer that is not v")
         args = self._lib.DiRegionAttnArgs(None, None, None, scores.data_ptr(), v.data_ptr(), y.data_ptr(), 0, 0, 0)
-        self._lib.check(self.lib.di_region_mix_batch(self._lib.DI_BF16, ctypes.byref(args), hb.items, hb.items_ptr,
+        self._lib.check(self.lib.di_region_mix_batch(self._dt(v), ctypes.byref(args), hb.items, hb.items_ptr,
                                                      hb.count, _stream()), "di_region_mix_batch")
         return y
 
@@ -610,7 +633,7 @@ class ResNet(nn.Module):
     def _forward_hipconv_batch(self, hb, x, spare, ops, cops, in_elu=False):
         """_forward_hipconv for every image of a HeadBatch at once: each pass is one launch over the
         packed buffers, the SE gate one di_se_gate launch in fp32 (the single path's gate goes through
-        torch's bf16 linears). x: the packed residual stream; spare: the other 128-channel buffer.
+        torch's linears in the head's dtype). The buffers are bf16 or fp32, as the batch is. x: the packed residual stream; spare: the other 128-channel buffer.
         Returns (the buffer holding the result, the free one)."""
         m = self._modules
         C = hb.CHANNELS
@@ -756,12 +779,12 @@ class ResNet2DInputWithOptAttention(nn.Module):
         return plan
 
     def body_batch(self, xs, native=False):
-        """body for several images in one launch sequence (bf16, HIP convolutions): xs is a list of
+        """body for several images in one launch sequence (HIP convolutions; a bf16 or an fp32 head): xs is a list of
         [1, 128, h, w] prologue outputs, or a HeadBatch whose ``input(i)`` views hold them. Returns
         the list of logits. Each image's logits are the same bits whatever else the batch holds.
         native: the same launches issued from C (di_head_body_batch, called on the plan's two parts) and
         phase2_conv(ELU(x)) of all images by one HIP launch (di_head_logits_batch) instead of two torch
-        kernels per image; the logits are views of one packed buffer. With the regional attention
+        kernels per image; the logits are views of one packed buffer; bf16 only. With the regional attention
         (use_attention) only native=False: its two blocks run inside the arena (_attention_batch)."""
         if native and self.use_attention:
             raise RuntimeError("body_batch(native=True) does not run the regional attention: di_head_body_batch "
@@ -769,12 +792,18 @@ class ResNet2DInputWithOptAttention(nn.Module):
         if getattr(self, "cops", None) is None or self.ops is None:
             raise RuntimeError("body_batch needs the HIP convolutions and norm passes (use_hip_convs, "
                                "use_hip_norm_ops)")
+        dtype = self.phase2_conv.weight.dtype
         if isinstance(xs, HeadBatch):
             hb = xs
         else:
-            hb = HeadBatch([x.shape[2:] for x in xs], xs[0].device)
+            hb = HeadBatch([x.shape[2:] for x in xs], xs[0].device, dtype=dtype)
             for i, x in enumerate(xs):
                 hb.input(i).copy_(x)
+        if hb.dtype != dtype:
+            raise ValueError(f"a {dtype} head takes a HeadBatch of that dtype, got {hb.dtype}")
+        if native and dtype != torch.bfloat16:
+            raise RuntimeError("body_batch(native=True) is bf16 only (di_head_body_batch, di_head_logits_batch); "
+                               "an fp32 head runs native=False")
         if native:
             # the staleness check reads ~850 parameters' pointers and versions (~0.25 ms): only those of the
             # first launches are checked before anything runs, the rest while the GPU works on these

@@ -89,7 +89,7 @@ class LitGINI(nn.Module):
                  dtype="f32", head_dtype=torch.float32, precise_head=False, fuse_head_prologue=False,
                  head_channels_last=False, head_hip_ops=True, head_convs="torch", pos_prob_threshold=0.5,
                  head_batch=0, head_batch_pixels=2 ** 22, head_body="python", use_interact_attention=False,
-                 num_interact_attention_heads=4, disable_geometric_mode=False, **kwargs):
+                 num_interact_attention_heads=4, disable_geometric_mode=False, head_batch_f32=0, **kwargs):
         super().__init__()
         # disable_geometric_mode (the reference's --disable_geometric_mode): the plain Graph Transformer
         # baseline in the GeoT's place, on its own HIP edge kernels (GeoTConfig, csrc/geot_plain.hip)
@@ -140,7 +140,7 @@ class LitGINI(nn.Module):
         # head_convs: "torch" (MIOpen), or the ResNets' 1x1 / dilated 3x3 convolutions on the matrix cores
         # with the norm + ELU fused into their loads (head.HeadConvOps), NCHW only: "hip" for the bf16 head
         # (di_head_conv), "hip_f32" for the fp32 one (di_head_conv_f32: fp32 storage, f32-input MFMA; one
-        # complex at a time -- the batched head and the native body are bf16 only).
+        # complex at a time, or in chunks with head_batch_f32 -- head_batch and the native body are bf16 only).
         if head_convs not in ("torch", "hip", "hip_f32"):
             raise ValueError(f'head_convs must be "torch", "hip" or "hip_f32", got {head_convs!r}')
         if head_convs == "hip" and (head_dtype != torch.bfloat16 or not head_hip_ops or head_channels_last):
@@ -163,6 +163,20 @@ class LitGINI(nn.Module):
         if head_batch > 0 and head_convs != "hip":
             raise ValueError('head_batch > 0 needs head_convs="hip" (the batched head runs on the HIP convolutions)')
         self.head_batch, self.head_batch_pixels = head_batch, head_batch_pixels
+        # head_batch_f32: head_batch for the fp32 parity head (head_convs="hip_f32"): N > 0 sends
+        # _forward_batch's complexes through the fp32 head's blocks in chunks of at most N complexes and at
+        # most head_batch_pixels pixels, every head kernel launched once per chunk (di_head_conv_f32_batch,
+        # di_plane_stats_f32_batch, di_se_scale_add_f32_batch). The fp32 arena takes 1536 B per pixel, so
+        # the default head_batch_pixels = 2**22 means 6 GiB: lower it where that is too much. A complex's
+        # logits are the same bits whatever else its chunk holds; they differ from head_batch_f32=0's in
+        # the last bits (the SE gate comes from di_se_gate's fp32 fmaf chain, not torch's fp32 linears).
+        head_batch_f32 = int(head_batch_f32)
+        if head_batch_f32 < 0:
+            raise ValueError("head_batch_f32 must be >= 0")
+        if head_batch_f32 > 0 and head_convs != "hip_f32":
+            raise ValueError('head_batch_f32 > 0 needs head_convs="hip_f32" (the batched fp32 head runs on the fp32 '
+                             'HIP convolutions; the bf16 head takes head_batch)')
+        self.head_batch_f32 = head_batch_f32
         # head_body: "python" issues the batched head's launches from ResNet._forward_hipconv_batch;
         # "native" issues the same launches from one C call per chunk (di_head_body_batch) and takes the
         # logits from one HIP launch (di_head_logits_batch). Same bits up to phase2_conv's input; it takes
@@ -248,7 +262,7 @@ class LitGINI(nn.Module):
                                + "; ".join(problems[:8]))
         opts = {k: kwargs[k] for k in ("dtype", "head_dtype", "precise_head", "fuse_head_prologue",
                                        "head_channels_last", "head_hip_ops", "head_convs", "head_batch",
-                                       "head_batch_pixels", "head_body") if k in kwargs}
+                                       "head_batch_pixels", "head_body", "head_batch_f32") if k in kwargs}
         model = cls(num_node_input_feats=cfg.num_node_input_feats, num_gnn_layers=cfg.num_gnn_layers,
                     num_gnn_hidden_channels=cfg.num_gnn_hidden_channels,
                     num_gnn_attention_heads=cfg.num_gnn_attention_heads, knn=cfg.knn,
@@ -319,7 +333,7 @@ class LitGINI(nn.Module):
         h2r = [off[b] for _, b in pairs]
         l1 = [gb.nodes_per_graph[a] for a, _ in pairs]
         l2 = [gb.nodes_per_graph[b] for _, b in pairs]
-        batched = self.head_batch > 0 or self.head_body == "native"
+        batched = self.head_batch > 0 or self.head_batch_f32 > 0 or self.head_body == "native"
         if prologue_op is not None and self.head_body == "native" and h.dtype == torch.bfloat16:
             logits = self._head_native_fused(prologue_op, h, h1r, h2r, l1, l2)
         elif prologue_op is not None:
@@ -333,9 +347,11 @@ class LitGINI(nn.Module):
         return logits, h, e
 
     def _head_chunks(self, shapes):
-        """Consecutive complexes in chunks of at most head_batch complexes and head_batch_pixels pixels."""
+        """Consecutive complexes in chunks of at most head_batch (an fp32 head: head_batch_f32) complexes and
+        head_batch_pixels pixels."""
         chunks, cur, px = [], [], 0
-        most = max(1, self.head_batch)  # head_batch=0 with head_body="native": chunks of one
+        # head_batch=0 with head_body="native": chunks of one; at most one of the two counts is set
+        most = max(1, self.head_batch, self.head_batch_f32)
         for i, (a, b) in enumerate(shapes):
             if cur and (len(cur) == most or px + a * b > self.head_batch_pixels):
                 chunks.append(cur)
@@ -347,15 +363,15 @@ class LitGINI(nn.Module):
         return chunks
 
     def _head_batched(self, views, prologue_done):
-        """The head over the complexes' views chunk by chunk (head_batch > 0): the prologue per complex,
-        written straight into the chunk's arena, then the blocks once for the whole chunk."""
+        """The head over the complexes' views chunk by chunk (head_batch / head_batch_f32 > 0): the prologue per
+        complex, written straight into the chunk's arena, then the blocks once for the whole chunk."""
         import contextlib
         im = self.interact_module
         logits = []
         # precise_head: conv2d_1 and phase2_conv (the two convolutions left on torch) as interact_forward
         with torch.backends.cudnn.flags(enabled=False) if self.precise_head else contextlib.nullcontext():
             for chunk in self._head_chunks([tuple(v.shape[2:]) for v in views]):
-                hb = HeadBatch([views[i].shape[2:] for i in chunk], views[chunk[0]].device)
+                hb = HeadBatch([views[i].shape[2:] for i in chunk], views[chunk[0]].device, dtype=self.head_dtype)
                 for slot, i in enumerate(chunk):
                     if prologue_done:
                         hb.input(slot).copy_(views[i])

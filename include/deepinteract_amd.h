@@ -448,6 +448,19 @@ int di_head_norm_fold(const void* stats, int32_t channels, int64_t hw, const flo
  * means, all fp32, each sum taken in index order by fused multiply-adds starting from the bias, so a
  * row's bits depend on nothing but that row. w1 [hidden, channels], w2 [channels, hidden] row-major.
  * channels 1 .. 1024, hidden 1 .. 64, count >= 1. One launch.
+ * The fp32 batch (the parity head, di_head_conv_f32's storage): packed ragged fp32 images, item i of a
+ * C-channel buffer at element offset C * px_off_i, with the same table, the same statistics buffer and
+ * the same rows. The bf16 entry points above keep refusing DI_F32; the fp32 forms are entry points of
+ * their own, as di_head_conv_f32 is:
+ *   di_head_conv_f32_batch     di_head_conv_batch's contract with fp32 x, weight and y (4-byte aligned);
+ *                              every item has the bits di_head_conv_f32 gives on that image
+ *   di_head_conv_f32_batch_check  its validation on the host, without a launch
+ *   di_plane_stats_f32_batch   di_plane_stats_batch for fp32: x 16-B aligned, channels a multiple of 4
+ *                              (items start 16-B aligned) and <= 128; the bits of di_plane_stats(DI_F32)
+ *   di_se_scale_add_f32_batch  di_se_scale_add_batch for fp32: 16-B aligned, channels a multiple of 4;
+ *                              the bits of di_se_scale_add(DI_F32)
+ * di_head_norm_fold_batch and di_se_gate hold no image dtype and serve both; di_region_scores_batch /
+ * di_region_mix_batch take DI_F32.
  * Asynchronous, no allocation, every refusal before any launch. DI_EINVAL: count < 1, a NULL table,
  * h or w < 1, offsets that the helper did not fill, or anything the single call refuses with
  * DI_EINVAL; DI_ERANGE: count > DI_BATCH_MAX, more than 2^40 pixels in all, or an item the single
@@ -466,6 +479,15 @@ int di_se_scale_add_batch(di_dtype dt, const void* x, const float* scale, const 
                           int32_t count, void* y, void* stream);
 int di_se_gate(const float* mean, const float* w1, const float* b1, const float* w2, const float* b2,
                int32_t count, int32_t channels, int32_t hidden, float* gate, void* stream);
+int di_head_conv_f32_batch(const di_head_conv_args* args, const di_head_item* items,
+                           const di_head_item* items_dev, int32_t count, void* stream);
+int di_head_conv_f32_batch_check(const di_head_conv_args* args, const di_head_item* items,
+                                 const di_head_item* items_dev, int32_t count);
+int di_plane_stats_f32_batch(const void* x, int32_t channels, const di_head_item* items,
+                             const di_head_item* items_dev, int32_t count, void* stats, void* stream);
+int di_se_scale_add_f32_batch(const void* x, const float* scale, const float* bias, const void* res,
+                              int32_t channels, const di_head_item* items, const di_head_item* items_dev,
+                              int32_t count, void* y, void* stream);
 
 /* ---- the whole contact-head body in one call (an addition to ABI 8) -------------------------
  * di_head_body_batch: everything between the prologue ELU(inorm_1(conv2d_1(T))) and phase2_conv

@@ -11,7 +11,12 @@ over all B complexes). The batch side builds its HeadBatch and copies the inputs
 region, as LitGINI._forward_batch does per chunk. ``launches`` counts the device kernels of one forward
 on each side (torch.profiler). Needs a GPU: there is no CPU path.
 
-usage: python tools/bench_head_batch.py [--reps 2] [--windows 5] [--out profiles/head_batch_bench.json]
+--f32: the fp32 parity head instead (head_convs="hip_f32": fp32 storage and weights, di_head_conv_f32 and
+the *_f32_batch passes; what head_batch_f32 runs per chunk) against a loop of single hip_f32 ``body`` calls
+in the same process, over 16 x 64^2, 16 x 145^2, 16 x 256^2 and 2 x 1000^2, into
+profiles/head_batch_f32_bench.json.
+
+usage: python tools/bench_head_batch.py [--f32] [--reps 2] [--windows 5] [--out profiles/head_batch_bench.json]
 """
 import argparse
 import json
@@ -29,6 +34,7 @@ from deepinteract_amd.head import HeadConvOps, HeadNormOps, ResNet2DInputWithOpt
 from deepinteract_amd.weights import seeded_state_dict  # noqa: E402
 
 CASES = tuple((b, side) for side in (64, 145, 256) for b in (1, 4, 16, 64)) + ((2, 1000),)
+CASES_F32 = ((16, 64), (16, 145), (16, 256), (2, 1000))
 
 
 def window(fn, reps):
@@ -66,12 +72,12 @@ def launches(fn):
                and "memcpy" not in ev.name.lower() and "memset" not in ev.name.lower())
 
 
-def head():
+def head(dtype=torch.bfloat16):
     sd = seeded_state_dict(0)
     hsd = {k[len("interact_module."):]: v for k, v in sd.items() if k.startswith("interact_module.")}
     m = ResNet2DInputWithOptAttention().cuda().eval()
     m.load_state_dict(hsd)
-    m = m.to(dtype=torch.bfloat16)
+    m = m.to(dtype=dtype)
     return m.use_hip_norm_ops(HeadNormOps("cuda")).use_hip_convs(HeadConvOps("cuda"))
 
 
@@ -80,17 +86,22 @@ def main():
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--cases", default="", help="B:side,... (default: the documented set)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "head_batch_bench.json"))
+    ap.add_argument("--f32", action="store_true", help="the fp32 parity head (hip_f32) and its documented cases")
+    ap.add_argument("--out", default="", help="default: profiles/head_batch_bench.json (--f32: "
+                                              "profiles/head_batch_f32_bench.json)")
     a = ap.parse_args()
+    dtype = torch.float32 if a.f32 else torch.bfloat16
+    out_path = a.out or os.path.join(ROOT, "profiles", "head_batch_f32_bench.json" if a.f32 else "head_batch_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_head_batch needs a ROCm GPU")
-    cases = tuple(tuple(int(v) for v in c.split(":")) for c in a.cases.split(",")) if a.cases else CASES
-    m = head()
+    cases = tuple(tuple(int(v) for v in c.split(":")) for c in a.cases.split(",")) if a.cases else \
+        (CASES_F32 if a.f32 else CASES)
+    m = head(dtype)
     g = torch.Generator(device="cuda").manual_seed(0)
     rows = []
     with torch.no_grad():
         for count, side in cases:
-            xs = [F.elu(torch.randn(1, 128, side, side, generator=g, device="cuda")).to(torch.bfloat16)
+            xs = [F.elu(torch.randn(1, 128, side, side, generator=g, device="cuda")).to(dtype)
                   for _ in range(count)]
 
             def batched():
@@ -107,13 +118,14 @@ def main():
             print(json.dumps(row), flush=True)
             del xs
             torch.cuda.empty_cache()
-    out = {"workload": "contact-head body (58 + 4 ResNet blocks + phase2_conv), bf16, HIP convolutions: body_batch "
+    kind = "fp32 (hip_f32)" if a.f32 else "bf16"
+    out = {"workload": f"contact-head body (58 + 4 ResNet blocks + phase2_conv), {kind}, HIP convolutions: body_batch "
                        "over B complexes vs a loop of B single-complex body calls",
            "device": torch.cuda.get_device_name(0), "reps_per_window": a.reps, "windows": a.windows,
            "timing": "HIP events on the current stream, median window, ms per forward over all B complexes",
            "results": rows}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
         json.dump(out, fh, indent=1)
         fh.write("\n")
 
