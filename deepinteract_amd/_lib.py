@@ -78,6 +78,18 @@ class DiAucItem(ctypes.Structure):
                 ("work_off", ctypes.c_int64)]
 
 
+DI_I64, DI_I32 = 0, 1
+DI_EX_OUTSIDE, DI_EX_LABEL, DI_EX_TWICE = 1, 2, 4
+DI_EX_BLOCK_ROWS = 1024
+
+
+class DiExamplesItem(ctypes.Structure):
+    _fields_ = [("examples", ctypes.c_void_p), ("logits", ctypes.c_void_p), ("labels", ctypes.c_void_p),
+                ("pool_logits", ctypes.c_void_p), ("pool_labels", ctypes.c_void_p), ("n", ctypes.c_int64),
+                ("out_off", ctypes.c_int64), ("total", ctypes.c_int64), ("work_off", ctypes.c_int64),
+                ("l1", ctypes.c_int32), ("l2", ctypes.c_int32)]
+
+
 class DiHeadConvArgs(ctypes.Structure):
     _fields_ = [("x", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("in_scale", ctypes.c_void_p),
                 ("in_shift", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("y", ctypes.c_void_p),
@@ -195,6 +207,11 @@ _SIGS = {
     "di_contact_rank_batch": ([_I, _P, _P, _I, ctypes.c_float, _P, _P], ctypes.c_int),
     "di_contact_auc_batch_work_bytes": ([_P, _I], ctypes.c_int64),
     "di_contact_auc_batch": ([_P, _P, _I, _P, _P], ctypes.c_int),
+    "di_examples_labels_work_bytes": ([_P, _I], ctypes.c_int64),
+    "di_examples_labels_batch": ([_I, _P, _P, _I, _P, _P], ctypes.c_int),
+    "di_examples_labels_batch_check": ([_I, _P, _P, _I, _P], ctypes.c_int),
+    "di_examples_gather_batch": ([_I, _I, _P, _P, _I, _P, _P], ctypes.c_int),
+    "di_examples_gather_batch_check": ([_I, _I, _P, _P, _I, _P], ctypes.c_int),
     "di_knn_topk": ([_I, _P, _P, _I, _I, _P, _P, _P], ctypes.c_int),
     "di_geo_feats": ([ctypes.POINTER(DiGeoArgs), _P], ctypes.c_int),
     "di_build_nbr_ids": ([_I, _P, _P, _P, ctypes.c_uint64, _P, _P], ctypes.c_int),

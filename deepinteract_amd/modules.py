@@ -8,8 +8,10 @@ Mirrors the Python API the reference's hot path exposes (deepinteract_modules.py
 * ``LitGINI`` (:1478): ``gnn_forward`` (:1660-1679), ``shared_step`` (:1687-1745),
   ``predict_step`` (:2178-2184), ``test_step`` (:2018-2101), plus ``predict_batch`` (the batched
   entry the benchmark and the distributed driver use), ``predict_contacts`` (the same with each
-  complex's ranked contacts), ``test_batch`` (test_step's figures for many complexes at once) and
-  ``test_epoch_end`` (:2103-2165, the medians and the top-k CSV).
+  complex's ranked contacts), ``test_batch`` (test_step's figures for many complexes at once),
+  ``test_epoch_end`` (:2103-2165, the medians and the top-k CSV), ``validation_step`` (:1915-1982, the
+  same figures on sampled example lists, a batch's complexes pooled), ``validation_batch`` (one such
+  dict per complex at once) and ``validation_epoch_end`` (:1984-2016, the medians).
 
 Graphs may be ``deepinteract_amd.graph.ResidueGraph`` or real ``dgl.DGLGraph`` objects.
 Batched graphs get per-chain semantics (each chain as the reference computes it at batch size 1).
@@ -25,8 +27,9 @@ from .config import GeoTConfig, NODE_COUNT_LIMIT, RESIDUE_COUNT_LIMIT
 from .engine import GeoTEngine, HeadPrologueOp, PairTensorOp, gpu_device
 from .graph import GraphBatch, ResidueGraph, batch as batch_graphs, unbatch
 from .head import HeadBatch, HeadConvOps, HeadNormOps, ResNet2DInputWithOptAttention, contact_probs
-from .ranking import (ContactAucOp, ContactRankOp, confusion_metrics, labels_from_examples,
-                      labels_from_examples_batch, topk_metrics)
+from ._lib import DI_RANK_MAX_K
+from .ranking import (ContactAucOp, ContactRankOp, ExamplesOp, confusion_metrics, labels_from_examples,
+                      labels_from_examples_batch, pooled_topk_metrics, topk_metrics)
 
 
 def _identity_embedding_sd(sd, cfg: GeoTConfig):
@@ -201,6 +204,7 @@ class LitGINI(nn.Module):
         self._dev_ops = None     # (device, GeoTEngine, PairTensorOp, HeadPrologueOp | None)
         self._rank_op = None     # ContactRankOp on the model's device
         self._auc_op = None      # ContactAucOp on the model's device
+        self._examples_op = None  # ExamplesOp on the model's device
 
     def load_reference_state_dict(self, sd):
         """Reference-keyed LitGINI state dict. The head loads into this nn.Module; the GeoT
@@ -504,6 +508,107 @@ class LitGINI(nn.Module):
             outs.append(out)
         return outs
 
+    def _examples(self):
+        dev = self.engine.device
+        if self._examples_op is None or self._examples_op.device != dev:
+            self._examples_op = ExamplesOp(dev)
+        return self._examples_op
+
+    @staticmethod
+    def _validation_k(l: int, n: int) -> int:
+        """Ranks kept of a pool of n rows: the largest k of the six figures that the pool and the
+        ranking's limit allow (l, or 10 for chains of fewer than 10 residues in all)."""
+        return min(max(l, 10), n, DI_RANK_MAX_K)
+
+    @staticmethod
+    def _validation_output(r, a, hits, l: int, n: int) -> dict:
+        """validation_step's dict from a pool's ranking (its counters), AUC record and host hits."""
+        confusion = {f: getattr(r, f) for f in ("tp", "fp", "fn", "tn")}
+        out = {"loss": r.ce_sum / n}
+        out.update({"val_" + name[5:]: v for name, v in confusion_metrics(**confusion).items()})
+        out["val_auroc"], out["val_auprc"] = a.auroc, a.auprc
+        out["confusion"] = confusion
+        out.update({"val_" + name: v for name, v in pooled_topk_metrics(hits, r.num_pos, l, n).items()})
+        return out
+
+    def validation_step(self, batch, batch_idx=0):
+        """LitGINI.validation_step (deepinteract_modules.py:1915-1982). batch = (graph1, graph2,
+        examples_list, filepaths); examples_list[i] is complex i's sampled [n_i, 3] (i, j, label)
+        rows: any count >= 1, any order, repeats allowed. As in the reference only the listed pairs
+        are judged, and the complexes of a batch are pooled: their rows, one complex after another,
+        form one list of N rows (ranking.ExamplesOp.gather), ranked and scored as one.
+
+        Returns loss (the mean cross-entropy over the N rows), val_acc / val_prec / val_recall /
+        val_f1 (ranking.confusion_metrics on the pool's counts at pos_prob_threshold), val_auroc /
+        val_auprc (ranking.ContactAucOp on the pool's probabilities; float('nan') when a class is
+        empty), confusion = {tp, fp, fn, tn}, and the six figures the reference logs:
+        val_top_10_prec, val_top_l_by_10_prec, val_top_l_by_5_prec, val_top_l_recall,
+        val_top_l_by_2_recall, val_top_l_by_5_recall with l = graph1.num_nodes() +
+        graph2.num_nodes() (ranking.pooled_topk_metrics: a k past the pool takes all N rows and
+        precision still divides by k; float('nan') where the reference would divide by zero, and
+        where k and N both exceed DI_RANK_MAX_K).
+
+        Equal probabilities rank by their position in the pooled list (the ranking op's stable
+        order); the reference's ``argsort`` leaves their order undefined."""
+        graph1, graph2, examples_list = batch[0], batch[1], batch[2]
+        logits_list = self.shared_step(graph1, graph2)
+        if len(examples_list) != len(logits_list):
+            raise ValueError("validation_step: one examples tensor per complex")
+        ex_op, rank = self._examples(), self._ranker()
+        (pool_logits, pool_labels), = ex_op.gather([lg.contiguous() for lg in logits_list],
+                                                   [ex.to(rank.device) for ex in examples_list],
+                                                   pools=[list(range(len(logits_list)))])
+        n = int(pool_labels.numel())
+        l = int(graph1.num_nodes()) + int(graph2.num_nodes())
+        r = rank(pool_logits, k=self._validation_k(l, n), labels=pool_labels, threshold=self.pos_prob_threshold)
+        a = self._auc()(r.probs, pool_labels)   # the map the ranking judged
+        return self._validation_output(r, a, r.hits.cpu(), l, n)
+
+    def validation_batch(self, gb: GraphBatch, pairs, examples_list):
+        """validation_step for many complexes at once, each complex its own pool and its own
+        l = L1 + L2: one forward (``_forward_batch``), one gather (ranking.ExamplesOp.gather), one
+        batched ranking call and one batched AUC call, whatever the number of complexes. pairs as in
+        ``predict_batch``; examples_list[i] belongs to complex i. Returns one validation_step dict per
+        complex, with the bits validation_step gives on that complex alone. The host reads the
+        device once for the lists' validation, once per metrics table and once for all top_hits."""
+        if len(pairs) != len(examples_list):
+            raise ValueError("validation_batch: one examples tensor per complex")
+        logits_list, _, _ = self._forward_batch(gb, pairs)
+        ex_op, rank, auc_op = self._examples(), self._ranker(), self._auc()
+        pooled = ex_op.gather([lg.contiguous() for lg in logits_list], [ex.to(rank.device) for ex in examples_list])
+        ls = [int(lg.shape[2]) + int(lg.shape[3]) for lg in logits_list]
+        ns = [int(lab.numel()) for _, lab in pooled]
+        ranks = rank.batch([lg for lg, _ in pooled], k=[self._validation_k(l, n) for l, n in zip(ls, ns)],
+                           labels_list=[lab for _, lab in pooled], threshold=self.pos_prob_threshold)
+        aucs = auc_op.batch([r.probs for r in ranks], [lab for _, lab in pooled])
+        hits = ranks.hits.cpu()
+        return [self._validation_output(r, a, hits[ranks.hits_off[i]:ranks.hits_off[i] + r.ids.numel()], l, n)
+                for i, (r, a, l, n) in enumerate(zip(ranks, aucs, ls, ns))]
+
+    _VAL_MEDIANS = ("val_acc", "val_prec", "val_recall", "val_f1", "val_auroc", "val_auprc")
+
+    def validation_epoch_end(self, outputs, group=None):
+        """LitGINI.validation_epoch_end (deepinteract_modules.py:1984-2016) without the loggers:
+        med_val_acc / prec / recall / f1 / auroc / auprc over the dicts of validation_step /
+        validation_batch, as ``test_epoch_end`` gives med_test_* (``torch.median``; with a process
+        ``group`` over every rank's values)."""
+        return self._epoch_medians(outputs, self._VAL_MEDIANS, group, "validation_epoch_end")
+
+    @staticmethod
+    def _epoch_medians(outputs, names, group, what) -> dict:
+        """med_<name> of this rank's outputs, or of every rank's (all-gathered; ranks may hold
+        different counts) with a process group."""
+        vals = [[float(o[name]) for name in names] for o in outputs]
+        if group is not None:
+            import torch.distributed as dist
+            gathered = [None] * dist.get_world_size(group)
+            dist.all_gather_object(gathered, vals, group=group)
+            vals = [row for part in gathered for row in part]
+        if not vals:
+            raise ValueError(f"{what}: no outputs")
+        table = torch.tensor(vals, dtype=torch.float64)
+        return {"med_" + name: float(torch.median(table[:, c])) for c, name in enumerate(names)}
+
     _MEDIANS = ("test_acc", "test_prec", "test_recall", "test_f1", "test_auroc", "test_auprc")
     _CSV_COLUMNS = ("top_10_prec", "top_l_by_10_prec", "top_l_by_5_prec", "top_l_recall", "top_l_by_2_recall",
                     "top_l_by_5_recall", "target")
@@ -518,16 +623,7 @@ class LitGINI(nn.Module):
         every rank returns the medians of all of them. With ``csv_path`` the six top-k columns plus
         ``target`` are written, one row per complex of THIS rank's outputs, in the layout
         ``DataFrame.to_csv`` writes (a leading unnamed index column; NaN as an empty field)."""
-        vals = [[float(o[name]) for name in self._MEDIANS] for o in outputs]
-        if group is not None:
-            import torch.distributed as dist
-            gathered = [None] * dist.get_world_size(group)
-            dist.all_gather_object(gathered, vals, group=group)
-            vals = [row for part in gathered for row in part]
-        if not vals:
-            raise ValueError("test_epoch_end: no outputs")
-        table = torch.tensor(vals, dtype=torch.float64)
-        out = {"med_" + name: float(torch.median(table[:, c])) for c, name in enumerate(self._MEDIANS)}
+        out = self._epoch_medians(outputs, self._MEDIANS, group, "test_epoch_end")
         if csv_path is not None:
             import csv
             with open(csv_path, "w", newline="") as fh:

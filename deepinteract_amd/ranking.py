@@ -21,7 +21,9 @@ test_acc / test_prec / test_recall / test_f1 from ``tp, fp, fn, tn``.
 ``ContactRankOp.batch`` / ``ContactAucOp.batch`` run either op over many complexes of different shapes
 with one launch sequence (``di_contact_rank_batch`` / ``di_contact_auc_batch``) and give every complex
 the bits of the single call; ``labels_from_examples_batch`` validates a batch's labels with one host
-read.
+read. ``ExamplesOp`` reads the example lists on the device (csrc/contact_examples.hip): complete lists
+as label maps, sampled lists as ``LitGINI.validation_step``'s pooled logits and labels;
+``pooled_topk_metrics`` is that step's top-k arithmetic.
 
 Out of scope: sending top-k lists instead of maps through ``predict_sharded``.
 """
@@ -371,6 +373,151 @@ class ContactAucOp:
         return out
 
 
+_EX_OUTSIDE = "examples: a pair index outside the complex"
+_EX_LABEL = "examples: labels must be 0 or 1"
+_EX_TWICE = "examples: a pair is missing or listed twice"
+
+
+class ExamplesOp:
+    """The reference's ``examples`` lists ([n, 3] rows of (i, j, label)) of a ragged batch on HIP
+    (csrc/contact_examples.hip): ``labels`` turns complete lists into the uint8 label maps the ranking
+    and AUC ops take, ``gather`` turns sampled lists into ``LitGINI.validation_step``'s pooled logits
+    and labels. One memset and one launch per DI_BATCH_MAX complexes, one host read (the flag words)
+    per call. No CPU fallback. Lists of int64 or int32 are read as they are when the whole batch has
+    one of the two widths; any other dtype, a mixed batch or a non-contiguous list is converted to
+    contiguous int64 first (a float list is truncated, as ``Tensor.to(torch.int64)`` does)."""
+
+    def __init__(self, device="cuda"):
+        self.device = gpu_device(device)
+        self.lib = _lib.load()
+
+    def _lists(self, examples_list):
+        """(index-width code, the lists as the kernels read them)."""
+        check_on(self.device, "ExamplesOp", *examples_list)
+        for ex in examples_list:
+            if ex.dim() != 2 or ex.shape[1] != 3:
+                raise ValueError("examples: [n, 3] rows of (i, j, label)")
+        if all(ex.dtype == torch.int32 for ex in examples_list):
+            return _lib.DI_I32, [ex.contiguous() for ex in examples_list]
+        return _lib.DI_I64, [ex.to(torch.int64).contiguous() for ex in examples_list]
+
+    @staticmethod
+    def _raise(flags, twice=True):
+        """The first complex with a flag raises; within it outside, then labels, then twice."""
+        for f in flags:
+            if f & _lib.DI_EX_OUTSIDE:
+                raise ValueError(_EX_OUTSIDE)
+            if f & _lib.DI_EX_LABEL:
+                raise ValueError(_EX_LABEL)
+            if twice and f & _lib.DI_EX_TWICE:
+                raise ValueError(_EX_TWICE)
+
+    def labels(self, examples_list, shapes):
+        """Complete lists (every pair of the complex exactly once) -> one uint8 [l1 * l2] map per
+        complex, views of one packed buffer that each start 16-B aligned. shapes[i] = (l1, l2).
+        Raises ``labels_from_examples_batch_torch``'s ValueErrors: a list of another shape or row
+        count; then, for the first complex that has a fault, an index outside it, a label other
+        than 0 / 1, a pair missing or listed twice, in this order."""
+        count = len(examples_list)
+        if count != len(shapes):
+            raise ValueError("examples: one (l1, l2) per complex")
+        if count < 1:
+            raise ValueError("examples: an empty batch")
+        idt, lists = self._lists(examples_list)
+        off, at = [], 0
+        for ex, (l1, l2) in zip(lists, shapes):
+            n = int(l1) * int(l2)
+            if n < 1:
+                raise ValueError(f"examples: an empty complex ({l1} x {l2})")
+            if ex.shape[0] != n:
+                raise ValueError(f"examples: {ex.shape[0]} rows for {l1} x {l2} = {n} pairs "
+                                 "(every pair exactly once)")
+            off.append(at)
+            at += (n + 15) // 16 * 16
+        maps = torch.empty(at, dtype=torch.uint8, device=self.device)
+        outs = [maps[o:o + int(l1) * int(l2)] for o, (l1, l2) in zip(off, shapes)]
+        items = (_lib.DiExamplesItem * count)()
+        for it, ex, out, (l1, l2) in zip(items, lists, outs, shapes):
+            it.examples, it.labels, it.n, it.l1, it.l2 = ex.data_ptr(), out.data_ptr(), ex.shape[0], l1, l2
+        flags = []
+        for lo in range(0, count, _lib.DI_BATCH_MAX):
+            m = min(_lib.DI_BATCH_MAX, count - lo)
+            part = (_lib.DiExamplesItem * m).from_buffer(items, lo * ctypes.sizeof(_lib.DiExamplesItem))
+            nb = self.lib.di_examples_labels_work_bytes(part, m)
+            if nb < 0:
+                raise ValueError(f"examples of a batch of {m}: code {nb} (l1 * l2 < 2^29)")
+            # its own workspace per launch: the flag words at its front are read after the last one
+            work = torch.empty(nb // 4, dtype=torch.int32, device=self.device)
+            part_dev = _table_to_device(part, self.device)
+            _lib.check(self.lib.di_examples_labels_batch(idt, part, _ptr(part_dev), m, _ptr(work), _stream()),
+                       "di_examples_labels_batch")
+            flags.append(work[:m])
+        self._raise((flags[0] if len(flags) == 1 else torch.cat(flags)).cpu().tolist())
+        return outs
+
+    def gather(self, logits_list, examples_list, pools=None):
+        """Sampled lists (any row count >= 1, any order, repeats allowed) -> per pool
+        ``(logits [1, 2, N, 1], labels [N] uint8)``: logits[0, c, r, 0] = the complex's
+        logits[0, c, i_r, j_r], bit for bit in the logits' dtype, and labels[r] = label_r, the rows of
+        the pool's complexes one after another (the reference's ``torch.cat``,
+        deepinteract_modules.py:1923-1932). Both go straight into ``ContactRankOp`` /
+        ``ContactAucOp``, which take the pooled list as an N x 1 map. logits_list: contiguous
+        [1, 2, L1, L2] tensors of one dtype (fp32 or bf16). pools: the complexes (indices into the
+        lists) that form each pool, every complex in exactly one; default: one pool per complex.
+        Raises ValueError for an index outside a complex or a label other than 0 / 1 (the first
+        complex with a fault, in this order)."""
+        count = len(logits_list)
+        if count < 1 or len(examples_list) != count:
+            raise ValueError("examples: one non-empty list of logits and one examples tensor per complex")
+        pools = [[i] for i in range(count)] if pools is None else [list(p) for p in pools]
+        if sorted(i for p in pools for i in p) != list(range(count)) or any(not p for p in pools):
+            raise ValueError("examples: every complex belongs to exactly one non-empty pool")
+        check_on(self.device, "ExamplesOp", *logits_list)
+        idt, lists = self._lists(examples_list)
+        dtype = logits_list[0].dtype
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"examples: fp32 / bf16 logits, got {dtype}")
+        for lg, ex in zip(logits_list, lists):
+            if lg.dim() != 4 or lg.shape[0] != 1 or lg.shape[1] != 2 or not lg.is_contiguous() or lg.numel() < 1:
+                raise ValueError("examples: one contiguous [1, 2, L1, L2] logits tensor per complex")
+            if lg.dtype != dtype:
+                raise TypeError("examples: one batch takes logits of one dtype")
+            if ex.shape[0] < 1:
+                raise ValueError("examples: a sampled list holds at least one row")
+        totals = [sum(lists[i].shape[0] for i in p) for p in pools]
+        lg_off, lab_off, at_lg, at_lab = [], [], 0, 0
+        for total in totals:      # every pool starts 16-B aligned in both buffers
+            lg_off.append(at_lg)
+            lab_off.append(at_lab)
+            at_lg += (2 * total + 7) // 8 * 8
+            at_lab += (total + 15) // 16 * 16
+        pool_logits = torch.empty(at_lg, dtype=dtype, device=self.device)
+        pool_labels = torch.empty(at_lab, dtype=torch.uint8, device=self.device)
+        out = [(pool_logits[a:a + 2 * t].view(1, 2, t, 1), pool_labels[b:b + t])
+               for a, b, t in zip(lg_off, lab_off, totals)]
+        items = (_lib.DiExamplesItem * count)()
+        for (plg, plab), members, total in zip(out, pools, totals):
+            at = 0
+            for i in members:
+                it, lg, ex = items[i], logits_list[i], lists[i]
+                it.examples, it.logits, it.pool_logits, it.pool_labels = (t.data_ptr() for t in (ex, lg, plg, plab))
+                it.n, it.out_off, it.total, it.l1, it.l2 = ex.shape[0], at, total, lg.shape[2], lg.shape[3]
+                at += ex.shape[0]
+        flags = torch.empty(count, dtype=torch.int32, device=self.device)
+        dt = _lib.DI_F32 if dtype == torch.float32 else _lib.DI_BF16
+        for lo in range(0, count, _lib.DI_BATCH_MAX):
+            m = min(_lib.DI_BATCH_MAX, count - lo)
+            part = (_lib.DiExamplesItem * m).from_buffer(items, lo * ctypes.sizeof(_lib.DiExamplesItem))
+            rc = self.lib.di_examples_gather_batch_check(dt, idt, part, ctypes.c_void_p(16), m, _ptr(flags[lo:]))
+            if rc < 0:
+                raise ValueError(f"examples of a batch of {m}: code {rc} (l1 * l2 < 2^29, a pool's rows < 2^31)")
+            part_dev = _table_to_device(part, self.device)
+            _lib.check(self.lib.di_examples_gather_batch(dt, idt, part, _ptr(part_dev), m, _ptr(flags[lo:]),
+                                                         _stream()), "di_examples_gather_batch")
+        self._raise(flags.cpu().tolist(), twice=False)
+        return out
+
+
 def confusion_metrics(tp, fp, fn, tn) -> dict:
     """test_acc / test_prec / test_recall / test_f1 of LitGINI.test_step from the confusion counts at
     pos_prob_threshold, as torchmetrics' multiclass (num_classes=2, average=None) metrics define them
@@ -394,9 +541,28 @@ def labels_from_examples(examples, l1: int, l2: int):
     return labels_from_examples_batch([examples], [(l1, l2)])[0]
 
 
+_examples_ops = {}   # device -> ExamplesOp, for labels_from_examples_batch
+
+
 def labels_from_examples_batch(examples_list, shapes):
     """``labels_from_examples`` for many complexes: shapes[i] = (l1, l2) of examples_list[i]. The same
-    validation and the same result per complex, with ONE host read for the whole batch."""
+    validation and the same result per complex, with ONE host read for the whole batch. Lists that
+    all lie on one GPU go through ``ExamplesOp.labels`` (one memset and one launch per DI_BATCH_MAX
+    complexes); anything else -- host tensors, an empty batch, an empty complex -- takes
+    ``labels_from_examples_batch_torch``. Results and errors are the same either way."""
+    devices = {ex.device for ex in examples_list}
+    if len(devices) == 1 and len(examples_list) == len(shapes) and all(a * b > 0 for a, b in shapes):
+        dev = next(iter(devices))
+        if dev.type == "cuda":
+            if dev not in _examples_ops:
+                _examples_ops[dev] = ExamplesOp(dev)
+            return _examples_ops[dev].labels(examples_list, shapes)
+    return labels_from_examples_batch_torch(examples_list, shapes)
+
+
+def labels_from_examples_batch_torch(examples_list, shapes):
+    """``labels_from_examples_batch`` in torch operations, on whatever device the lists are on: the
+    path of host tensors, and the yardstick ``ExamplesOp.labels`` is tested and measured against."""
     if len(examples_list) != len(shapes):
         raise ValueError("examples: one (l1, l2) per complex")
     flags, outs = [], []
@@ -457,5 +623,39 @@ def topk_metrics(hits, num_pos, l: int) -> dict:
             "top_l_recall": recall(l), "top_l_by_2_recall": recall(l // 2), "top_l_by_5_recall": recall(l // 5)}
 
 
+def pooled_topk_metrics(hits, num_pos, l: int, n: int) -> dict:
+    """The six top-k figures of LitGINI.validation_step (``top_10_prec`` .. ``top_l_by_5_recall``; the
+    step logs them as ``val_`` + name) for a pooled list of ``n`` sampled rows, from ``hits`` (hits[r] =
+    positives among ranks 0..r of the pool, as many ranks as were kept) with the reference's
+    arithmetic (deepinteract_utils.py:977-995) and its k's: 10, l // 10, l // 5 (precision), l,
+    l // 2, l // 5 (recall), l = graph1.num_nodes() + graph2.num_nodes(). Unlike test_step's maps a
+    pool may be shorter than k: the reference's slice ``[:k]`` then takes all n rows (num_pos
+    positives), and precision still divides by k.
+
+    A figure is float('nan') where the reference would divide by zero (k = 0; num_pos = 0 for a
+    recall), where k and n both exceed DI_RANK_MAX_K (the ranking is cut there), and where fewer than
+    min(k, n) ranks were kept."""
+    K, num_pos, n = len(hits), int(num_pos), int(n)
+
+    def top(k):
+        if k < 1 or (k > _lib.DI_RANK_MAX_K and n > _lib.DI_RANK_MAX_K):
+            return None
+        if k >= n:
+            return num_pos
+        return None if k > K else int(hits[k - 1])
+
+    def prec(k):
+        h = top(k)
+        return float("nan") if h is None else h / k
+
+    def recall(k):
+        h = top(k)
+        return float("nan") if h is None or num_pos == 0 else h / num_pos
+
+    return {"top_10_prec": prec(10), "top_l_by_10_prec": prec(l // 10), "top_l_by_5_prec": prec(l // 5),
+            "top_l_recall": recall(l), "top_l_by_2_recall": recall(l // 2), "top_l_by_5_recall": recall(l // 5)}
+
+
 __all__ = ["ContactRankOp", "ContactRanking", "ContactRankingBatch", "ContactAucOp", "ContactAuc",
-           "confusion_metrics", "labels_from_examples", "labels_from_examples_batch", "topk_metrics"]
+           "ExamplesOp", "confusion_metrics", "labels_from_examples", "labels_from_examples_batch",
+           "labels_from_examples_batch_torch", "pooled_topk_metrics", "topk_metrics"]

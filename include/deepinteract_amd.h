@@ -38,6 +38,8 @@
  *   di_contact_auc   test_step's exact per-complex test_auroc / test_auprc (class 1)
  *                                                                    deepinteract_modules.py:2018-2101
  *   di_contact_rank_batch / di_contact_auc_batch  both over many complexes in one launch sequence
+ *   di_examples_labels_batch / di_examples_gather_batch  a batch's example lists as label maps, or
+ *                     as validation_step's pooled logits and labels  deepinteract_modules.py:1915-1982
  *
  * Module-at-a-time entry points (deepinteract_amd/layers.py; same math as the fused kernels):
  *   di_conformation   ConformationModule.forward                      deepinteract_modules.py:373-455
@@ -709,6 +711,59 @@ int di_contact_rank_batch(int32_t dtype, const di_rank_item* items, const di_ran
 int64_t di_contact_auc_batch_work_bytes(di_auc_item* items, int32_t count);
 int di_contact_auc_batch(const di_auc_item* items, const di_auc_item* items_dev, int32_t count,
                          void* work, void* stream);
+
+/* ---- example lists of a ragged batch (an addition to ABI 8) ---------------------------------
+ * The reference's `examples` [n, 3] = (i, j, label) rows of `count` complexes, contiguous, int64
+ * (DI_I64) or int32 (DI_I32; one width per call), turned into what the two ops above take: one memset
+ * and ONE launch, whatever count is. Tables and grid as for di_contact_rank_batch (host items
+ * validated and used for grid sizes; items_dev the caller's device copy).
+ *   di_examples_labels_batch  complete lists (n == l1 * l2, every pair exactly once):
+ *                             labels[i * l2 + j] = label, uint8 [l1 * l2]
+ *   di_examples_gather_batch  sampled lists as LitGINI.validation_step reads them
+ *                             (deepinteract_modules.py:1915-1982; n >= 1, any order, repeats allowed):
+ *                             pool_logits[c * total + out_off + r] = logits[c, i_r, j_r] (c = 0, 1;
+ *                             logits [2, l1, l2] in `dtype`, copied bit for bit) and
+ *                             pool_labels[out_off + r] = label_r (uint8). A pool is the reference's
+ *                             torch.cat over the complexes of one validation batch: its items carry
+ *                             the pool's base pointers and row count `total`, and their own place
+ *                             out_off in it. Any number of pools per call.
+ * Flags, one int32 per complex, device memory, cleared by the call: DI_EX_OUTSIDE an index outside
+ * the complex; DI_EX_LABEL a label other than 0 / 1; DI_EX_TWICE (labels only) a pair listed twice.
+ * With n == l1 * l2, no DI_EX_OUTSIDE and no DI_EX_TWICE every pair is covered. The flags are a
+ * function of the lists alone (agent-scope atomicOr on a 1-bit-per-pair bitmap, the returned word
+ * tested; see csrc/contact_examples.hip). Indices are compared in their own width: 2^40 or -1 is
+ * outside. A row that is outside touches no memory but its flag, and writes nothing; a flagged
+ * complex's outputs are unspecified, its neighbours' are not affected.
+ *   labels: flags are the first `count` words of `work` (di_examples_labels_work_bytes bytes, 16-B
+ *   aligned, cleared in-stream by the call); the helper fills work_off (the complex's bitmap), and the
+ *   call refuses other values. gather: flags [count] is the caller's.
+ * Asynchronous, no allocation, every refusal before any launch; the *_check forms do the same
+ * validation on the host, without a launch. DI_EINVAL: count < 1, a NULL table / work / flags, a bad
+ * dtype or index width, an item with a NULL pointer its mode uses, n < 1, l1 or l2 < 1, a pointer off
+ * its element's alignment, labels with n != l1 * l2 or a work_off the helper did not fill, gather
+ * with total < 1 or rows outside the pool (out_off < 0, out_off + n > total). DI_ERANGE:
+ * count > DI_BATCH_MAX, l1 * l2 >= 2^29, total >= 2^31. */
+enum { DI_I64 = 0, DI_I32 = 1 };
+enum { DI_EX_OUTSIDE = 1, DI_EX_LABEL = 2, DI_EX_TWICE = 4 };
+#define DI_EX_BLOCK_ROWS 1024   /* rows of one list a block takes (a wave: 64 consecutive rows at a time) */
+typedef struct {
+  const void* examples;
+  const void* logits;
+  uint8_t* labels;
+  void* pool_logits;
+  uint8_t* pool_labels;
+  int64_t n, out_off, total, work_off;
+  int32_t l1, l2;
+} di_examples_item;
+int64_t di_examples_labels_work_bytes(di_examples_item* items, int32_t count);
+int di_examples_labels_batch(int32_t idx_dtype, const di_examples_item* items, const di_examples_item* items_dev,
+                             int32_t count, void* work, void* stream);
+int di_examples_labels_batch_check(int32_t idx_dtype, const di_examples_item* items,
+                                   const di_examples_item* items_dev, int32_t count, const void* work);
+int di_examples_gather_batch(int32_t dtype, int32_t idx_dtype, const di_examples_item* items,
+                             const di_examples_item* items_dev, int32_t count, int32_t* flags, void* stream);
+int di_examples_gather_batch_check(int32_t dtype, int32_t idx_dtype, const di_examples_item* items,
+                                   const di_examples_item* items_dev, int32_t count, const int32_t* flags);
 
 /* ---- graph builder ----------------------------------------------------------------------- */
 /* Cα kNN per chain: idx_out [Nt,k] chain-local neighbour ids (ascending squared distance,
