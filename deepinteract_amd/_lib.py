@@ -207,6 +207,7 @@ _SIGS = {
     "di_contact_rank_batch": ([_I, _P, _P, _I, ctypes.c_float, _P, _P], ctypes.c_int),
     "di_contact_auc_batch_work_bytes": ([_P, _I], ctypes.c_int64),
     "di_contact_auc_batch": ([_P, _P, _I, _P, _P], ctypes.c_int),
+    "di_rank_record_bytes": ([_I, _I, _I, _I, ctypes.POINTER(ctypes.c_int64)], ctypes.c_int64),
     "di_examples_labels_work_bytes": ([_P, _I], ctypes.c_int64),
     "di_examples_labels_batch": ([_I, _P, _P, _I, _P, _P], ctypes.c_int),
     "di_examples_labels_batch_check": ([_I, _P, _P, _I, _P], ctypes.c_int),
@@ -267,6 +268,20 @@ def load_variant(path: str):
         raise RuntimeError(f"variant library {path} does not exist")
     _lib = _bind(path)
     return _lib
+
+
+RECORD_FIELDS = ("ids", "scores", "hits", "metrics", "auc")
+
+
+def rank_record_layout(l1: int, l2: int, k: int, with_labels: bool):
+    """``di_rank_record_bytes``: (the record's bytes, {field: byte offset} of RECORD_FIELDS; a field the
+    record does not have is absent). The layout is the C function's alone. ValueError where it refuses."""
+    offs = (ctypes.c_int64 * 5)()
+    nb = load().di_rank_record_bytes(int(l1), int(l2), int(k), int(bool(with_labels)), offs)
+    if nb < 0:
+        raise ValueError(f"ranking record of a {l1} x {l2} complex, k = {k}: code {nb} "
+                         f"(1 <= k <= min(L1 * L2, {DI_RANK_MAX_K}), L1 * L2 < 2^29)")
+    return int(nb), {f: int(o) for f, o in zip(RECORD_FIELDS, offs) if o >= 0}
 
 
 def check(rc: int, what: str):

@@ -672,6 +672,28 @@ extern "C" int64_t di_contact_rank_work_bytes(int64_t n, int32_t k) {
   return RK_FIXED_BYTES + (int64_t)k * (int64_t)sizeof(unsigned long long);
 }
 
+// The wire record of one complex's ranking: ids | scores | hits | pad to 8 | di_rank_metrics |
+// di_auc_metrics | pad to 16 (the last three and hits only with labels). Host arithmetic only.
+extern "C" int64_t di_rank_record_bytes(int32_t l1, int32_t l2, int32_t k, int32_t with_labels, int64_t* offsets) {
+  if (l1 < 1 || l2 < 1 || (with_labels != 0 && with_labels != 1)) return DI_EINVAL;
+  const int rc = rank_check_sizes((int64_t)l1 * (int64_t)l2, k);
+  if (rc != DI_OK) return rc;
+  const int64_t k4 = (int64_t)k * 4;  // <= 16 KiB
+  int64_t off[5] = {0, k4, -1, -1, -1};
+  int64_t at = 2 * k4;
+  if (with_labels) {
+    off[2] = at;
+    at = (at + k4 + 7) / 8 * 8;
+    off[3] = at;
+    at += (int64_t)sizeof(di_rank_metrics);
+    off[4] = at;
+    at += (int64_t)sizeof(di_auc_metrics);
+  }
+  if (offsets)
+    for (int i = 0; i < 5; ++i) offsets[i] = off[i];
+  return (at + 15) / 16 * 16;
+}
+
 extern "C" int di_contact_rank(int32_t dtype, const void* logits, int32_t l1, int32_t l2, int32_t k,
                                const uint8_t* labels, float threshold, float* probs, int32_t* top_ids,
                                float* top_scores, int32_t* top_hits, di_rank_metrics* metrics, void* work,

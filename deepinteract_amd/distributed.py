@@ -22,6 +22,13 @@ lit_model_predict.py:236-239 does).
   with an asynchronous ``all_gather_into_tensor`` issued as soon as they exist, so the collective
   of round c runs on the process group's stream while round c+1 computes) or ONCE after the last
   micro-batch (``all_gather_maps``). Both return bit-identical maps.
+* ``predict_sharded(gather="topk")`` -- a third wire format: per complex one fixed-layout record
+  (``di_rank_record_bytes``: its K best contacts and, with labels, test_step's counters and AUC
+  figures) instead of its L1 * L2 map; ``ranked_forward`` is its HIP forward, whose ranking and AUC
+  kernels write the records straight into the send buffer, and ``RecordPlan`` their places in it.
+  ONE all-gather moves them. ``test_sharded`` builds ``LitGINI.test_step``'s dict for every complex
+  on every rank from them (the reference gathers per-step results the same way,
+  deepinteract_modules.py:2114-2119).
 """
 from __future__ import annotations
 
@@ -199,8 +206,58 @@ class ChunkedGather:
         return out
 
 
+class RecordPlan:
+    """Where every complex's wire record lies, computed by every rank from the sizes, the plan and k
+    alone (no communication): rank r's records follow each other in its size-sorted local order (so
+    a micro-batch's records are contiguous), each ``di_rank_record_bytes`` long, and every rank's
+    part of the receive buffer is as wide as the largest rank's. ``ks[i]`` = ``ranking.record_k`` of
+    complex i; a K beyond DI_RANK_MAX_K raises ValueError here, on every rank alike, before any
+    collective. ``place[i]`` = (owner rank, byte offset in the owner's send buffer);
+    ``rank_bytes[r]``; ``width`` = bytes of one rank's part (>= 16); ``send_bytes`` / ``recv_bytes``
+    = what one rank sends and holds."""
+
+    def __init__(self, sizes, plan, k=None, with_labels=False):
+        from . import _lib
+        from .ranking import record_k
+        self.sizes, self.plan, self.with_labels = list(sizes), plan, bool(with_labels)
+        self.ks = [record_k(l1, l2, k) for l1, l2 in self.sizes]
+        self.place, self.rank_bytes = [None] * len(self.sizes), []
+        for r, p in enumerate(plan):
+            at = 0
+            for i in local_order(self.sizes, p):
+                self.place[i] = (r, at)
+                at += _lib.rank_record_layout(*self.sizes[i], self.ks[i], self.with_labels)[0]
+            self.rank_bytes.append(at)
+        self.width = max(max(self.rank_bytes, default=0), 16)
+        self.send_bytes, self.recv_bytes = self.width, len(plan) * self.width
+
+
+def _predict_topk(complexes, forward, sizes, plan, micro_batch, device, group, k, with_labels):
+    from .ranking import GatheredRanking, RecordSlot, _HostCopy
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    rp = RecordPlan(sizes, plan, k, with_labels)      # raises on every rank alike, before any collective
+    # zero-filled once: padding, and the buffer of a rank that owns nothing, are deterministic
+    send = torch.zeros(rp.width // 4, dtype=torch.int32, device=device)
+    recv = torch.empty(world * rp.width // 4, dtype=torch.int32, device=device)
+    mine = local_order(sizes, plan[rank])
+    for s in range(0, len(mine), micro_batch):
+        ids = mine[s:s + micro_batch]
+        slots = [RecordSlot(send, rp.place[i][1], *sizes[i], rp.ks[i], with_labels) for i in ids]
+        forward([complexes[i] for i in ids], ids, out=slots)
+    if send.is_cuda and dist.get_backend(group) == "gloo":
+        # gloo is a host transport: the finished buffer crosses to the host and back, still one collective
+        host = torch.empty(recv.shape, dtype=recv.dtype)
+        dist.all_gather_into_tensor(host, send.cpu(), group=group)
+        recv.copy_(host)
+    else:
+        dist.all_gather_into_tensor(recv, send, group=group)
+    table = _HostCopy(recv)
+    return [GatheredRanking(recv, r * rp.width + off, *sizes[i], rp.ks[i], with_labels, table)
+            for i, (r, off) in enumerate(rp.place)], plan
+
+
 def predict_sharded(complexes: Sequence, forward: Callable, micro_batch: int = 8, dtype=torch.float32,
-                    device=None, group=None, gather: str = "chunked"):
+                    device=None, group=None, gather: str = "chunked", k=None, with_labels: bool = False):
     """C4 driver: every rank runs ``forward`` over its contiguous shard of
     ``complexes`` in size-sorted micro-batches; every complex's contact map ends on every rank.
 
@@ -212,7 +269,20 @@ def predict_sharded(complexes: Sequence, forward: Callable, micro_batch: int = 8
     with the next round's compute (ChunkedGather); "once" -- ONE all-gather after the last
     micro-batch (all_gather_maps); "none" -- no collective, this rank's maps only (timing the
     compute alone). Returns the maps (global order; None for other ranks' complexes with "none")
-    and the plan."""
+    and the plan.
+
+    gather="topk": ranked contacts and metrics instead of maps. Sharding, micro-batches and plan are
+    the same; what crosses the wire is one record per complex (``RecordPlan``; ``k``: ranks kept,
+    None = min(L1, L2), an int = min(k, L1 * L2); ``with_labels``: the records also carry top_hits,
+    di_rank_metrics and di_auc_metrics). One int32 send buffer for the whole call and the receive
+    buffer are allocated up front on ``device``; the forward is called as ``forward(batch, ids,
+    out=slots)`` with ``slots`` the complexes' ``ranking.RecordSlot`` views of the send buffer, which it
+    must fill (``ranked_forward``); ``dtype`` is not used. After the last micro-batch exactly ONE
+    ``all_gather_into_tensor`` is issued for the call, not one per round: a record is a few KB
+    (12 KB at 1000 x 1000 with labels against a 4 MB map), so per-round collectives would be bound by
+    their latency, not by bytes, and there is nothing worth overlapping. Returns one
+    ``ranking.GatheredRanking`` per complex in global order, views of the receive buffer on ``device``,
+    and the plan. A K beyond DI_RANK_MAX_K raises ValueError on every rank before any collective."""
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     sizes = [(int(len(c[0]["backbone"])), int(len(c[1]["backbone"]))) for c in complexes]
@@ -220,8 +290,11 @@ def predict_sharded(complexes: Sequence, forward: Callable, micro_batch: int = 8
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(group) == "nccl" \
             else torch.device("cpu")
-    if gather not in ("chunked", "once", "none"):
-        raise ValueError(f"gather {gather!r}: one of chunked, once, none")
+    if gather not in ("chunked", "once", "none", "topk"):
+        raise ValueError(f"gather {gather!r}: one of chunked, once, none, topk")
+    if gather == "topk":
+        return _predict_topk(complexes, forward, sizes, plan, micro_batch, torch.device(device), group, k,
+                             with_labels)
     chunks = ChunkedGather(sizes, plan, micro_batch, dtype, device, group) if gather == "chunked" else None
     mine = local_order(sizes, plan[rank])
     maps = {}
@@ -244,3 +317,107 @@ def predict_sharded(complexes: Sequence, forward: Callable, micro_batch: int = 8
     if gather == "none":
         return [maps.get(i) for i in range(len(sizes))], plan
     return all_gather_maps([maps[i] for i in plan[rank]], plan, sizes, dtype, device, group), plan
+
+
+def ranked_forward(model, k: int = 20, seed: int = 0, examples=None, filepaths=None, auc_max_pos=None):
+    """The per-micro-batch forward of ``predict_sharded(gather="topk")`` on the HIP path: on-device
+    graph build with ``gpu_forward``'s seeding rule (complex i's chains draw their neighbour-edge ids
+    from seed + 2i + s; ``k`` is the graphs' neighbour count) -> the model's batched forward ->
+    ``ContactRankOp.batch(out=slots)``, whose kernels write each complex's ids and scores -- with
+    ``examples`` also top_hits and di_rank_metrics -- into its record in the send buffer. The ranks
+    kept are the slots' (``RecordPlan.ks``).
+
+    examples (optional): every complex's [L1 * L2, 3] example list, indexed by global id (filepaths
+    likewise; the forward itself does not read them). Then ``labels_from_examples_batch`` goes first and
+    ``ContactAucOp.batch(out=slots)`` follows, on the maps the ranking stored. A complex with more
+    positives than ``auc_max_pos`` (None: the op's default) must be finished by its owner before the
+    collective: the micro-batch's records are read once (one copy of their span of the send buffer),
+    and every complex whose record says overflow is run again through the single op with
+    max_pos = num_pos, writing the same record, in stream order before the send."""
+    import ctypes
+
+    from . import _lib
+    from .builder import build_graph_batch
+    from .ranking import labels_from_examples_batch
+
+    if examples is not None and filepaths is not None and len(examples) != len(filepaths):
+        raise ValueError("ranked_forward: one file path per examples tensor")
+
+    def fn(complexes, ids, out):
+        if len(out) != len(ids):
+            raise ValueError("ranked_forward: one record slot per complex")
+        if any(slot.with_labels != (examples is not None) for slot in out):
+            raise ValueError("ranked_forward: records carry labels exactly when examples are given")
+        chains = [c for pair in complexes for c in pair]
+        dev = model.engine.device
+        gb = build_graph_batch(chains, k=k, device=dev, node_count_limit=model.cfg.node_count_limit,
+                               nbr_seeds=[seed + 2 * i + s for i in ids for s in (0, 1)])
+        with torch.no_grad():
+            logits, _, _ = model._forward_batch(gb, [(2 * j, 2 * j + 1) for j in range(len(complexes))])
+            logits = [lg.contiguous() for lg in logits]
+            rank = model._ranker()
+            ks = [slot.k for slot in out]
+            if examples is None:
+                rank.batch(logits, k=ks, threshold=model.pos_prob_threshold, out=out)
+                return out
+            shapes = [(int(lg.shape[2]), int(lg.shape[3])) for lg in logits]
+            labels = labels_from_examples_batch([examples[i].to(rank.device) for i in ids], shapes)
+            ranks = rank.batch(logits, k=ks, labels_list=labels, threshold=model.pos_prob_threshold, out=out)
+            auc_op = model._auc()
+            max_pos = None if auc_max_pos is None else [min(int(auc_max_pos), a * b) for a, b in shapes]
+            auc_op.batch([r.probs for r in ranks], labels, max_pos=max_pos, out=out)
+            # the owner finishes overflowed complexes: one read of the micro-batch's span of records
+            buf = out[0].buffer
+            lo = min(slot.byte_off for slot in out)
+            hi = max(slot.byte_off + slot.nbytes for slot in out)
+            host = buf[lo // 4:hi // 4].cpu().numpy().tobytes()
+            for slot, r, lab in zip(out, ranks, labels):
+                at = slot.byte_off - lo + slot.offsets["auc"]
+                m = _lib.DiAucMetrics.from_buffer_copy(host[at:at + ctypes.sizeof(_lib.DiAucMetrics)])
+                if m.overflow:
+                    auc_op._run(r.probs, lab, int(m.num_pos), out=slot.auc)
+        return out
+
+    return fn
+
+
+def test_sharded(model, complexes, examples_list, filepaths, micro_batch: int = 8, k: int = 20, seed: int = 0,
+                 group=None, device=None, auc_max_pos=None):
+    """``LitGINI.test_step`` over a sharded test set: ``predict_sharded(gather="topk",
+    with_labels=True)`` with ``ranked_forward`` (``k``: the graphs' neighbour count, ``seed`` its
+    seeding), then one dict per complex, in global order, on EVERY rank, decoded from the gathered
+    records with one host copy. The keys are ``LitGINI.test_batch``'s, from the same host arithmetic
+    (``topk_metrics`` over the record's top_hits with l = min(L1, L2), ``confusion_metrics``,
+    loss = ce_sum / (L1 * L2), the record's auroc / auprc), so every figure has the bits of a
+    single-process ``test_batch``. ``test_preds`` / ``test_preds_rounded`` / ``test_labels`` are
+    None: maps are not sent. ``top_ids`` / ``top_scores`` (numpy, the min(L1, L2) best contacts) are
+    added. The list goes to ``model.test_epoch_end(outs)`` WITHOUT a group: every rank already holds
+    every row. device: where the buffers live (default: the model's GPU)."""
+    import os
+
+    from .ranking import confusion_metrics, topk_metrics
+    if not (len(complexes) == len(examples_list) == len(filepaths)):
+        raise ValueError("test_sharded: one examples tensor and one file path per complex")
+    if device is None:
+        device = model.engine.device
+    forward = ranked_forward(model, k=k, seed=seed, examples=examples_list, filepaths=filepaths,
+                             auc_max_pos=auc_max_pos)
+    recs, _ = predict_sharded(complexes, forward, micro_batch=micro_batch, device=device, group=group,
+                              gather="topk", k=None, with_labels=True)
+    outs = []
+    for rec, path in zip(recs, filepaths):
+        l = min(rec.l1, rec.l2)
+        confusion = {f: getattr(rec, f) for f in ("tp", "fp", "fn", "tn")}
+        out = {"loss": rec.ce_sum / (rec.l1 * rec.l2)}
+        out.update(topk_metrics(rec.host_array("hits"), rec.num_pos, l))
+        out["test_preds"] = out["test_preds_rounded"] = out["test_labels"] = None
+        out["target"] = str(path).split(os.sep)[-1][:4]
+        out["confusion"] = confusion
+        out["test_auroc"], out["test_auprc"] = rec.auroc, rec.auprc
+        out.update(confusion_metrics(**confusion))
+        out["top_ids"], out["top_scores"] = rec.host_array("ids"), rec.host_array("scores")
+        outs.append(out)
+    return outs
+
+
+test_sharded.__test__ = False    # a driver, not a pytest case

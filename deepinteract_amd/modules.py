@@ -508,6 +508,16 @@ class LitGINI(nn.Module):
             outs.append(out)
         return outs
 
+    def test_sharded(self, complexes, examples_list, filepaths, micro_batch=8, k=20, seed=0, group=None,
+                     device=None):
+        """test_step over a test set sharded across a process group (``distributed.test_sharded``):
+        every rank ranks and scores its shard on the device, ONE all-gather moves a KB-sized record
+        per complex, and every rank returns every complex's test_batch dict (maps None; ``top_ids`` /
+        ``top_scores`` added), ready for ``test_epoch_end(outs)`` without a group."""
+        from .distributed import test_sharded
+        return test_sharded(self, complexes, examples_list, filepaths, micro_batch=micro_batch, k=k, seed=seed,
+                            group=group, device=device)
+
     def _examples(self):
         dev = self.engine.device
         if self._examples_op is None or self._examples_op.device != dev:

@@ -25,7 +25,11 @@ read. ``ExamplesOp`` reads the example lists on the device (csrc/contact_example
 as label maps, sampled lists as ``LitGINI.validation_step``'s pooled logits and labels;
 ``pooled_topk_metrics`` is that step's top-k arithmetic.
 
-Out of scope: sending top-k lists instead of maps through ``predict_sharded``.
+Across ranks: ``ContactRankOp.batch(out=...)`` / ``ContactAucOp.batch(out=...)`` write a complex's
+ranked contacts and metrics into caller memory -- ``RecordSlot``, the views of one wire record
+(``di_rank_record_bytes`` lays it out) in a collective's send buffer -- with the bits they have
+without ``out``; ``GatheredRanking`` reads a received record. ``distributed.predict_sharded(gather=
+"topk")`` sends these records instead of the maps.
 """
 from __future__ import annotations
 
@@ -95,6 +99,138 @@ class ContactRanking:
         raise AttributeError(name)
 
 
+def record_k(l1: int, l2: int, k=None) -> int:
+    """Ranks a wire record keeps of an (l1, l2) complex: min(l1, l2) for k = None (test_step's
+    l), else min(k, l1 * l2). A function of the sizes and the caller's k alone, so every rank of a
+    process group computes every record's size. ValueError for k < 1 or a result beyond DI_RANK_MAX_K."""
+    kk = min(int(l1), int(l2)) if k is None else min(int(k), int(l1) * int(l2))
+    if kk < 1 or kk > _lib.DI_RANK_MAX_K:
+        raise ValueError(f"a {l1} x {l2} complex with k = {k} keeps {kk} ranks: 1 <= ranks <= {_lib.DI_RANK_MAX_K}")
+    return kk
+
+
+_WORDS = {"metrics": ctypes.sizeof(_lib.DiRankMetrics) // 4, "auc": ctypes.sizeof(_lib.DiAucMetrics) // 4}
+
+
+class RecordSlot:
+    """The fields of one wire record (``_lib.rank_record_layout``: ``di_rank_record_bytes``) as views of
+    ``buffer``, a contiguous 1-D int32 tensor, starting ``byte_off`` bytes into it: ``ids`` int32 [k],
+    ``scores`` fp32 [k] and, with labels, ``hits`` int32 [k], ``metrics`` int64 [6] (di_rank_metrics)
+    and ``auc`` int64 [8] (di_auc_metrics); None without labels. These are what ``ContactRankOp.batch``
+    and ``ContactAucOp.batch`` take as ``out``. ValueError for a buffer of another dtype or layout, a
+    record that does not start 16-B aligned or does not fit."""
+
+    def __init__(self, buffer, byte_off: int, l1: int, l2: int, k: int, with_labels: bool):
+        if buffer.dtype != torch.int32 or buffer.dim() != 1 or not buffer.is_contiguous():
+            raise ValueError("record buffer: a contiguous 1-D int32 tensor")
+        self.nbytes, self.offsets = _lib.rank_record_layout(l1, l2, k, with_labels)
+        byte_off = int(byte_off)
+        if byte_off < 0 or (buffer.data_ptr() + byte_off) % 16:
+            raise ValueError(f"record at byte {byte_off}: records start 16-B aligned")
+        if byte_off + self.nbytes > buffer.numel() * 4:
+            raise ValueError(f"record of {self.nbytes} bytes at byte {byte_off} does not fit "
+                             f"a buffer of {buffer.numel() * 4} bytes")
+        self.buffer, self.byte_off, self.l1, self.l2, self.k = buffer, byte_off, int(l1), int(l2), int(k)
+        self.with_labels = bool(with_labels)
+
+        def words(field, count):
+            if field not in self.offsets:
+                return None
+            at = (byte_off + self.offsets[field]) // 4
+            return buffer[at:at + count]
+
+        self.ids = words("ids", k)
+        self.scores = words("scores", k).view(torch.float32)
+        self.hits = words("hits", k)
+        self.metrics, self.auc = (None if w is None else w.view(torch.int64)
+                                  for w in (words(f, _WORDS[f]) for f in ("metrics", "auc")))
+
+
+class _HostCopy:
+    """A gathered record buffer, brought to the host once (which waits for the stream it was written on)
+    when the first record asks for a number."""
+
+    def __init__(self, buffer):
+        self.buffer, self._host = buffer, None
+
+    def bytes(self, lo: int, hi: int) -> bytes:
+        if self._host is None:
+            import numpy as np
+            self._host = self.buffer.cpu().numpy().view(np.uint8)
+        return self._host[lo:hi].tobytes()
+
+
+class GatheredRanking:
+    """One complex's received wire record (``distributed.predict_sharded(gather="topk")``): ``ids``
+    [K] int32 flat indices in rank order, ``scores`` [K] fp32, ``pairs`` [K, 2] their (i, j), ``hits``
+    [K] int32 (None without labels), all views of the receive buffer on its device; ``probs`` is None
+    (maps are not sent). ``metrics()`` / ``auc()`` decode the record's di_rank_metrics /
+    di_auc_metrics, and ContactRanking's names (``num_pos, tp, fp, fn, tn, ce_sum``) and ``auroc`` /
+    ``auprc`` read them; the records of one call share one host copy of the buffer (``host``)."""
+
+    probs = None
+    _FIELDS = ContactRanking._FIELDS
+    _AUC_FIELDS = tuple(f for f, _ in _lib.DiAucMetrics._fields_ if f != "pad")
+
+    def __init__(self, buffer, byte_off, l1, l2, k, with_labels, host=None):
+        slot = RecordSlot(buffer, byte_off, l1, l2, k, with_labels)
+        self.ids, self.scores, self.hits = slot.ids, slot.scores, slot.hits
+        self.buffer, self.byte_off, self.nbytes = buffer, slot.byte_off, slot.nbytes
+        self.l1, self.l2, self.with_labels = slot.l1, slot.l2, slot.with_labels
+        self._at = {f: byte_off + o for f, o in slot.offsets.items()}
+        self._host = _HostCopy(buffer) if host is None else host
+        self._decoded = {}
+
+    @property
+    def pairs(self):
+        i = torch.div(self.ids, self.l2, rounding_mode="floor")
+        return torch.stack((i, self.ids - i * self.l2), dim=1)
+
+    def _struct(self, field, ctype, names):
+        if not self.with_labels:
+            raise ValueError("the record was sent without labels")
+        if field not in self._decoded:
+            lo = self._at[field]
+            m = ctype.from_buffer_copy(self._host.bytes(lo, lo + ctypes.sizeof(ctype)))
+            self._decoded[field] = {f: getattr(m, f) for f in names}
+        return self._decoded[field]
+
+    def host_array(self, field):
+        """ids / scores / hits as a numpy array, from the shared host copy."""
+        import numpy as np
+        k = self.ids.numel()
+        lo = self._at[field]
+        return np.frombuffer(self._host.bytes(lo, lo + 4 * k),
+                             dtype=np.float32 if field == "scores" else np.int32).copy()
+
+    def metrics(self) -> dict:
+        return self._struct("metrics", _lib.DiRankMetrics, self._FIELDS)
+
+    def auc(self) -> dict:
+        return self._struct("auc", _lib.DiAucMetrics, self._AUC_FIELDS)
+
+    def __getattr__(self, name):
+        if name in GatheredRanking._FIELDS:
+            return self.metrics()[name] if self.with_labels else None
+        if name in ("auroc", "auprc"):
+            return self.auc()[name] if self.with_labels else None
+        raise AttributeError(name)
+
+
+def _check_out(what, t, dtype, length, align, device):
+    """An output handed in by the caller is what the op would have allocated itself."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"out: {what} is missing")
+    if t.dtype != dtype or t.dim() != 1 or t.numel() != length or not t.is_contiguous():
+        raise ValueError(f"out: {what} is a contiguous {dtype} tensor of {length} elements, "
+                         f"got {t.dtype} {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"out: {what} on {t.device}, the kernels run on {device}")
+    if t.data_ptr() % align:
+        raise ValueError(f"out: {what} is not {align}-B aligned")
+    return t
+
+
 class ContactRankOp:
     """softmax(logits)[1], its K best contacts and test_step's counters for one complex on HIP.
 
@@ -154,7 +290,7 @@ class ContactRankOp:
                                             _ptr(work), _stream()), "di_contact_rank")
         return ContactRanking(probs, ids, scores, hits, metrics, l2)
 
-    def batch(self, logits_list, k=None, labels_list=None, threshold=0.5):
+    def batch(self, logits_list, k=None, labels_list=None, threshold=0.5, out=None):
         """The op over many complexes of different shapes with ONE launch sequence per DI_BATCH_MAX
         complexes (``di_contact_rank_batch``): a ``ContactRankingBatch`` (a list) of ``ContactRanking``,
         each with the bits the single call gives on the same inputs. logits_list: [1, 2, L1, L2]
@@ -163,10 +299,21 @@ class ContactRankOp:
         the single op's, applied to every element. The outputs are views of packed buffers (one
         allocation per kind; every map starts 16-B aligned); the descriptor table goes to the device
         with one pinned, non-blocking copy on the current stream; the results share one metrics
-        table, read from the device once, on first use."""
+        table, read from the device once, on first use.
+
+        out (optional): one slot per complex (``RecordSlot``, or anything with these attributes) whose
+        ``ids`` int32 [k], ``scores`` fp32 [k] and, with labels, ``hits`` int32 [k] and ``metrics``
+        int64 [6] (8-B aligned) tensors receive the outputs instead of the op's own buffers: the item
+        table's top_ids / top_scores / top_hits / metrics pointers name them, the kernels and every
+        output bit are those of the call without ``out``, and nothing is packed or copied afterwards.
+        Another dtype, length, device, layout or alignment raises ValueError before any launch. The
+        maps stay the op's own allocation; the batch's packed ``hits`` is None, and each result reads
+        its own metrics record."""
         count = len(logits_list)
         if count < 1:
             raise ValueError("contact ranking: an empty batch")
+        if out is not None and len(out) != count:
+            raise ValueError("contact ranking: one out slot per complex")
         ks = list(k) if isinstance(k, (list, tuple)) else [k] * count
         if labels_list is not None and len(labels_list) != count or len(ks) != count:
             raise ValueError("contact ranking: one k and one labels tensor per complex")
@@ -185,26 +332,39 @@ class ContactRankOp:
             at_map += (l1 * l2 + 3) // 4 * 4
             at_k += kk
         dev = self.device
-        probs = torch.empty(at_map, dtype=torch.float32, device=dev)
-        ids = torch.empty(at_k, dtype=torch.int32, device=dev)
-        scores = torch.empty(at_k, dtype=torch.float32, device=dev)
         words = ctypes.sizeof(_lib.DiRankMetrics) // 8
-        hits = torch.empty(at_k, dtype=torch.int32, device=dev) if with_labels else None
-        metrics = torch.empty(count, words, dtype=torch.int64, device=dev) if with_labels else None
-        table = _MetricsTable(metrics) if with_labels else None
-        out = ContactRankingBatch()
-        out.hits, out.hits_off = hits, tuple(k_off)
+        if out is not None:     # the caller's memory: checked against what is allocated below
+            for slot, (_, _, _, kk) in zip(out, checked):
+                _check_out("ids", slot.ids, torch.int32, kk, 4, dev)
+                _check_out("scores", slot.scores, torch.float32, kk, 4, dev)
+                if with_labels:
+                    _check_out("hits", slot.hits, torch.int32, kk, 4, dev)
+                    _check_out("metrics", slot.metrics, torch.int64, words, 8, dev)
+        probs = torch.empty(at_map, dtype=torch.float32, device=dev)
+        ids = scores = hits = metrics = table = None
+        if out is None:
+            ids = torch.empty(at_k, dtype=torch.int32, device=dev)
+            scores = torch.empty(at_k, dtype=torch.float32, device=dev)
+            hits = torch.empty(at_k, dtype=torch.int32, device=dev) if with_labels else None
+            metrics = torch.empty(count, words, dtype=torch.int64, device=dev) if with_labels else None
+            table = _MetricsTable(metrics) if with_labels else None
+        res = ContactRankingBatch()
+        res.hits, res.hits_off = hits, tuple(k_off)
         items = (_lib.DiRankItem * count)()
         for i, (lg, (_, l1, l2, kk)) in enumerate(zip(logits_list, checked)):
             n = l1 * l2
-            r = ContactRanking(probs[map_off[i]:map_off[i] + n].view(l1, l2), ids[k_off[i]:k_off[i] + kk],
-                               scores[k_off[i]:k_off[i] + kk], hits[k_off[i]:k_off[i] + kk] if with_labels else None,
-                               metrics[i] if with_labels else None, l2, table, i)
-            out.append(r)
+            if out is None:
+                mine = (ids[k_off[i]:k_off[i] + kk], scores[k_off[i]:k_off[i] + kk],
+                        hits[k_off[i]:k_off[i] + kk] if with_labels else None, metrics[i] if with_labels else None)
+            else:
+                mine = (out[i].ids, out[i].scores, out[i].hits if with_labels else None,
+                        out[i].metrics if with_labels else None)
+            r = ContactRanking(probs[map_off[i]:map_off[i] + n].view(l1, l2), *mine, l2, table, i)
+            res.append(r)
             it = items[i]
             it.logits, it.probs, it.top_ids, it.top_scores = (t.data_ptr() for t in (lg, r.probs, r.ids, r.scores))
             if with_labels:
-                it.labels, it.top_hits, it.metrics = labels_list[i].data_ptr(), r.hits.data_ptr(), metrics[i].data_ptr()
+                it.labels, it.top_hits, it.metrics = labels_list[i].data_ptr(), r.hits.data_ptr(), mine[3].data_ptr()
             it.l1, it.l2, it.k = l1, l2, kk
         for lo in range(0, count, _lib.DI_BATCH_MAX):
             m = min(_lib.DI_BATCH_MAX, count - lo)
@@ -215,7 +375,7 @@ class ContactRankOp:
             work, part_dev = _grow(self, nb), _table_to_device(part, dev)
             _lib.check(self.lib.di_contact_rank_batch(dt, part, _ptr(part_dev), m, ctypes.c_float(threshold),
                                                       _ptr(work), _stream()), "di_contact_rank_batch")
-        return out
+        return res
 
 
 def _grow(op, nbytes):
@@ -314,10 +474,15 @@ class ContactAucOp:
                              "(1 <= max_pos <= n < 2^29)")
         return _grow(self, nb)
 
-    def _run(self, probs, labels, max_pos):
+    def _run(self, probs, labels, max_pos, out=None):
+        """One complex through di_contact_auc; out (optional): the int64 [8] record to write."""
         n = probs.numel()
         work = self._workspace(n, max_pos)
-        out = torch.empty(ctypes.sizeof(_lib.DiAucMetrics) // 8, dtype=torch.int64, device=self.device)
+        words = ctypes.sizeof(_lib.DiAucMetrics) // 8
+        if out is None:
+            out = torch.empty(words, dtype=torch.int64, device=self.device)
+        else:
+            _check_out("auc", out, torch.int64, words, 8, self.device)
         _lib.check(self.lib.di_contact_auc(_ptr(probs), _ptr(labels), n, max_pos, _ptr(out), _ptr(work), _stream()),
                    "di_contact_auc")
         return ContactAuc(out, max_pos)
@@ -329,7 +494,7 @@ class ContactAucOp:
         res._rerun = lambda num_pos: self._run(probs, labels, num_pos)   # keeps probs and labels alive
         return res
 
-    def batch(self, probs_list, labels_list, max_pos=None):
+    def batch(self, probs_list, labels_list, max_pos=None, out=None):
         """The op over many complexes of different shapes with ONE launch sequence per DI_BATCH_MAX
         complexes (``di_contact_auc_batch``): a list of ``ContactAuc``, each with the bits the single
         call gives on the same inputs. max_pos: None (the default per complex), one int, or one per
@@ -337,10 +502,20 @@ class ContactAucOp:
         table goes to the device with one pinned, non-blocking copy on the current stream; the results
         share one metrics table, read from the device once, on first use; a complex that overflowed
         its max_pos is rerun alone through the single op on that read, and leaves its neighbours'
-        figures as they are."""
+        figures as they are.
+
+        out (optional): per complex the int64 [8], 8-B aligned tensor (or a ``RecordSlot``, whose
+        ``auc`` is one) that receives its di_auc_metrics instead of a row of the op's table: the items'
+        out pointers name them, with the bits of the call without ``out``. Another dtype, length,
+        device, layout or alignment raises ValueError before any launch. Each result then reads its
+        own record; a rerun after an overflow still writes a buffer of the op's (the caller that must
+        have the rerun's figures in its memory calls ``_run(..., out=...)``, as
+        ``distributed.ranked_forward`` does)."""
         count = len(probs_list)
         if count < 1:
             raise ValueError("contact AUC: an empty batch")
+        if out is not None and len(out) != count:
+            raise ValueError("contact AUC: one out record per complex")
         mps = list(max_pos) if isinstance(max_pos, (list, tuple)) else [max_pos] * count
         if len(labels_list) != count or len(mps) != count:
             raise ValueError("contact AUC: one labels tensor and one max_pos per complex")
@@ -350,17 +525,21 @@ class ContactAucOp:
             if self.lib.di_contact_auc_work_bytes(probs_list[i].numel(), mps[i]) < 0:
                 self._workspace(probs_list[i].numel(), mps[i])    # raises as the single op does
         words = ctypes.sizeof(_lib.DiAucMetrics) // 8
-        metrics = torch.empty(count, words, dtype=torch.int64, device=self.device)
-        table = _MetricsTable(metrics)
+        if out is None:
+            metrics = torch.empty(count, words, dtype=torch.int64, device=self.device)
+            table = _MetricsTable(metrics)
+        else:
+            metrics = [_check_out("auc", getattr(o, "auc", o), torch.int64, words, 8, self.device) for o in out]
+            table = None
         items = (_lib.DiAucItem * count)()
-        out = []
+        results = []
         for i, (probs, labels) in enumerate(zip(probs_list, labels_list)):
             it = items[i]
             it.probs, it.labels, it.out = probs.data_ptr(), labels.data_ptr(), metrics[i].data_ptr()
             it.n, it.max_pos = probs.numel(), mps[i]
             res = ContactAuc(metrics[i], mps[i], None, table, i)
             res._rerun = lambda num_pos, p=probs, y=labels: self._run(p, y, num_pos)   # keeps both alive
-            out.append(res)
+            results.append(res)
         for lo in range(0, count, _lib.DI_BATCH_MAX):
             m = min(_lib.DI_BATCH_MAX, count - lo)
             part = (_lib.DiAucItem * m).from_buffer(items, lo * ctypes.sizeof(_lib.DiAucItem))
@@ -370,7 +549,7 @@ class ContactAucOp:
             work, part_dev = _grow(self, nb), _table_to_device(part, self.device)
             _lib.check(self.lib.di_contact_auc_batch(part, _ptr(part_dev), m, _ptr(work), _stream()),
                        "di_contact_auc_batch")
-        return out
+        return results
 
 
 _EX_OUTSIDE = "examples: a pair index outside the complex"
@@ -657,5 +836,5 @@ def pooled_topk_metrics(hits, num_pos, l: int, n: int) -> dict:
 
 
 __all__ = ["ContactRankOp", "ContactRanking", "ContactRankingBatch", "ContactAucOp", "ContactAuc",
-           "ExamplesOp", "confusion_metrics", "labels_from_examples", "labels_from_examples_batch",
+           "ExamplesOp", "GatheredRanking", "RecordSlot", "record_k", "confusion_metrics", "labels_from_examples", "labels_from_examples_batch",
            "labels_from_examples_batch_torch", "pooled_topk_metrics", "topk_metrics"]

@@ -712,6 +712,28 @@ int64_t di_contact_auc_batch_work_bytes(di_auc_item* items, int32_t count);
 int di_contact_auc_batch(const di_auc_item* items, const di_auc_item* items_dev, int32_t count,
                          void* work, void* stream);
 
+/* ---- one complex's ranking as a wire record (an addition to ABI 8) ----------------------------
+ * What a rank sends of a complex instead of its map (distributed.predict_sharded, gather="topk"):
+ * the outputs of di_contact_rank(_batch) and di_contact_auc(_batch) laid side by side, so that the
+ * items' top_ids / top_scores / top_hits / metrics / out pointers can name the collective's send
+ * buffer and no pack, cast or copy runs between the ops and the send. For a complex of shape
+ * (l1, l2) with k kept ranks:
+ *   offsets[0]  top_ids     int32[k]
+ *   offsets[1]  top_scores  float[k]
+ *   offsets[2]  top_hits    int32[k]          with labels only
+ *               (pad to 8 B)
+ *   offsets[3]  di_rank_metrics               with labels only
+ *   offsets[4]  di_auc_metrics                with labels only
+ *               (pad to 16 B)
+ * Every field is made of 4- or 8-byte words and starts on its word size, given a record that starts
+ * 16-B aligned; records laid end to end stay 16-B aligned. Returns the record's bytes and, where
+ * offsets is not NULL, the five byte offsets from its start (-1 for a field the record does not
+ * have). Host arithmetic only: nothing is launched, no device is touched.
+ * DI_EINVAL: l1 or l2 < 1, k < 1, k > l1 * l2, with_labels other than 0 / 1. DI_ERANGE:
+ * k > DI_RANK_MAX_K, l1 * l2 >= 2^29 (the sizes di_contact_rank refuses, with its codes). */
+int64_t di_rank_record_bytes(int32_t l1, int32_t l2, int32_t k, int32_t with_labels,
+                             int64_t* offsets /* 5 field offsets, may be NULL */);
+
 /* ---- example lists of a ragged batch (an addition to ABI 8) ---------------------------------
  * The reference's `examples` [n, 3] = (i, j, label) rows of `count` complexes, contiguous, int64
  * (DI_I64) or int32 (DI_I32; one width per call), turned into what the two ops above take: one memset
