@@ -90,6 +90,19 @@ class DiExamplesItem(ctypes.Structure):
                 ("l1", ctypes.c_int32), ("l2", ctypes.c_int32)]
 
 
+DI_IF_OFFSETS, DI_IF_EMPTY, DI_IF_NONFINITE = 1, 2, 4
+
+
+class DiInterfaceItem(ctypes.Structure):
+    _fields_ = [("xyz0", ctypes.c_void_p), ("res_off0", ctypes.c_void_p), ("xyz1", ctypes.c_void_p),
+                ("res_off1", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("l1", ctypes.c_int32),
+                ("l2", ctypes.c_int32), ("a0", ctypes.c_int32), ("a1", ctypes.c_int32), ("work_off", ctypes.c_int64)]
+
+
+class DiInterfaceStats(ctypes.Structure):
+    _fields_ = [("num_pos", ctypes.c_int64), ("flags", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
 class DiHeadConvArgs(ctypes.Structure):
     _fields_ = [("x", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("in_scale", ctypes.c_void_p),
                 ("in_shift", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("y", ctypes.c_void_p),
@@ -213,6 +226,9 @@ _SIGS = {
     "di_examples_labels_batch_check": ([_I, _P, _P, _I, _P], ctypes.c_int),
     "di_examples_gather_batch": ([_I, _I, _P, _P, _I, _P, _P], ctypes.c_int),
     "di_examples_gather_batch_check": ([_I, _I, _P, _P, _I, _P], ctypes.c_int),
+    "di_interface_work_bytes": ([_P, _I], ctypes.c_int64),
+    "di_interface_labels_batch": ([_P, _P, _I, ctypes.c_float, _P, _P], ctypes.c_int),
+    "di_interface_labels_batch_check": ([_P, _P, _I, ctypes.c_float, _P], ctypes.c_int),
     "di_knn_topk": ([_I, _P, _P, _I, _I, _P, _P, _P], ctypes.c_int),
     "di_geo_feats": ([ctypes.POINTER(DiGeoArgs), _P], ctypes.c_int),
     "di_build_nbr_ids": ([_I, _P, _P, _P, ctypes.c_uint64, _P, _P], ctypes.c_int),

@@ -319,7 +319,8 @@ def predict_sharded(complexes: Sequence, forward: Callable, micro_batch: int = 8
     return all_gather_maps([maps[i] for i in plan[rank]], plan, sizes, dtype, device, group), plan
 
 
-def ranked_forward(model, k: int = 20, seed: int = 0, examples=None, filepaths=None, auc_max_pos=None):
+def ranked_forward(model, k: int = 20, seed: int = 0, examples=None, filepaths=None, auc_max_pos=None,
+                   structures=None, cutoff: float = 6.0):
     """The per-micro-batch forward of ``predict_sharded(gather="topk")`` on the HIP path: on-device
     graph build with ``gpu_forward``'s seeding rule (complex i's chains draw their neighbour-edge ids
     from seed + 2i + s; ``k`` is the graphs' neighbour count) -> the model's batched forward ->
@@ -333,21 +334,37 @@ def ranked_forward(model, k: int = 20, seed: int = 0, examples=None, filepaths=N
     positives than ``auc_max_pos`` (None: the op's default) must be finished by its owner before the
     collective: the micro-batch's records are read once (one copy of their span of the send buffer),
     and every complex whose record says overflow is run again through the single op with
-    max_pos = num_pos, writing the same record, in stream order before the send."""
+    max_pos = num_pos, writing the same record, in stream order before the send.
+
+    structures (instead of examples; both: ValueError): every complex's ((xyz0, res_off0), (xyz1,
+    res_off1)) heavy atoms, indexed by global id, as ``LitGINI.test_batch_structures`` takes them. The
+    label maps then come from ``ranking.InterfaceOp`` (``cutoff`` in A) and everything after them is
+    the same; only the micro-batch's own atoms go to this rank's device. A chain whose residue count
+    differs from its complex's raises ValueError before the micro-batch's first launch."""
     import ctypes
 
     from . import _lib
     from .builder import build_graph_batch
     from .ranking import labels_from_examples_batch
 
-    if examples is not None and filepaths is not None and len(examples) != len(filepaths):
-        raise ValueError("ranked_forward: one file path per examples tensor")
+    if examples is not None and structures is not None:
+        raise ValueError("ranked_forward: labels from examples or from structures, not both")
+    given = examples if examples is not None else structures
+    if given is not None and filepaths is not None and len(given) != len(filepaths):
+        raise ValueError("ranked_forward: one file path per examples tensor / structure")
 
     def fn(complexes, ids, out):
         if len(out) != len(ids):
             raise ValueError("ranked_forward: one record slot per complex")
-        if any(slot.with_labels != (examples is not None) for slot in out):
-            raise ValueError("ranked_forward: records carry labels exactly when examples are given")
+        if any(slot.with_labels != (given is not None) for slot in out):
+            raise ValueError("ranked_forward: records carry labels exactly when examples or structures are given")
+        if structures is not None:
+            for i, (c1, c2) in zip(ids, complexes):
+                want = (len(c1["backbone"]), len(c2["backbone"]))
+                got = tuple(int(chain[1].shape[0]) - 1 for chain in structures[i])
+                if got != want:
+                    raise ValueError(f"ranked_forward: complex {i}'s structure has {got} residues, "
+                                     f"its chains {want}")
         chains = [c for pair in complexes for c in pair]
         dev = model.engine.device
         gb = build_graph_batch(chains, k=k, device=dev, node_count_limit=model.cfg.node_count_limit,
@@ -357,11 +374,15 @@ def ranked_forward(model, k: int = 20, seed: int = 0, examples=None, filepaths=N
             logits = [lg.contiguous() for lg in logits]
             rank = model._ranker()
             ks = [slot.k for slot in out]
-            if examples is None:
+            if given is None:
                 rank.batch(logits, k=ks, threshold=model.pos_prob_threshold, out=out)
                 return out
             shapes = [(int(lg.shape[2]), int(lg.shape[3])) for lg in logits]
-            labels = labels_from_examples_batch([examples[i].to(rank.device) for i in ids], shapes)
+            if examples is not None:
+                labels = labels_from_examples_batch([examples[i].to(rank.device) for i in ids], shapes)
+            else:
+                labels = model._interface().labels([structures[i][0] for i in ids], [structures[i][1] for i in ids],
+                                                   cutoff=cutoff)
             ranks = rank.batch(logits, k=ks, labels_list=labels, threshold=model.pos_prob_threshold, out=out)
             auc_op = model._auc()
             max_pos = None if auc_max_pos is None else [min(int(auc_max_pos), a * b) for a, b in shapes]
@@ -382,7 +403,7 @@ def ranked_forward(model, k: int = 20, seed: int = 0, examples=None, filepaths=N
 
 
 def test_sharded(model, complexes, examples_list, filepaths, micro_batch: int = 8, k: int = 20, seed: int = 0,
-                 group=None, device=None, auc_max_pos=None):
+                 group=None, device=None, auc_max_pos=None, structures=None, cutoff: float = 6.0):
     """``LitGINI.test_step`` over a sharded test set: ``predict_sharded(gather="topk",
     with_labels=True)`` with ``ranked_forward`` (``k``: the graphs' neighbour count, ``seed`` its
     seeding), then one dict per complex, in global order, on EVERY rank, decoded from the gathered
@@ -392,16 +413,21 @@ def test_sharded(model, complexes, examples_list, filepaths, micro_batch: int = 
     single-process ``test_batch``. ``test_preds`` / ``test_preds_rounded`` / ``test_labels`` are
     None: maps are not sent. ``top_ids`` / ``top_scores`` (numpy, the min(L1, L2) best contacts) are
     added. The list goes to ``model.test_epoch_end(outs)`` WITHOUT a group: every rank already holds
-    every row. device: where the buffers live (default: the model's GPU)."""
+    every row. device: where the buffers live (default: the model's GPU).
+
+    The labels come from ``examples_list`` or, with ``examples_list=None``, from ``structures``
+    (``ranked_forward``; ``cutoff`` in A): exactly one of the two is not None (ValueError otherwise)."""
     import os
 
     from .ranking import confusion_metrics, topk_metrics
-    if not (len(complexes) == len(examples_list) == len(filepaths)):
-        raise ValueError("test_sharded: one examples tensor and one file path per complex")
+    if (examples_list is None) == (structures is None):
+        raise ValueError("test_sharded: exactly one of examples_list and structures")
+    if not (len(complexes) == len(examples_list if structures is None else structures) == len(filepaths)):
+        raise ValueError("test_sharded: one examples tensor (or structure) and one file path per complex")
     if device is None:
         device = model.engine.device
     forward = ranked_forward(model, k=k, seed=seed, examples=examples_list, filepaths=filepaths,
-                             auc_max_pos=auc_max_pos)
+                             auc_max_pos=auc_max_pos, structures=structures, cutoff=cutoff)
     recs, _ = predict_sharded(complexes, forward, micro_batch=micro_batch, device=device, group=group,
                               gather="topk", k=None, with_labels=True)
     outs = []

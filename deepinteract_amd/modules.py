@@ -28,7 +28,7 @@ from .engine import GeoTEngine, HeadPrologueOp, PairTensorOp, gpu_device
 from .graph import GraphBatch, ResidueGraph, batch as batch_graphs, unbatch
 from .head import HeadBatch, HeadConvOps, HeadNormOps, ResNet2DInputWithOptAttention, contact_probs
 from ._lib import DI_RANK_MAX_K
-from .ranking import (ContactAucOp, ContactRankOp, ExamplesOp, confusion_metrics, labels_from_examples,
+from .ranking import (ContactAucOp, ContactRankOp, ExamplesOp, InterfaceOp, confusion_metrics, labels_from_examples,
                       labels_from_examples_batch, pooled_topk_metrics, topk_metrics)
 
 
@@ -205,6 +205,7 @@ class LitGINI(nn.Module):
         self._rank_op = None     # ContactRankOp on the model's device
         self._auc_op = None      # ContactAucOp on the model's device
         self._examples_op = None  # ExamplesOp on the model's device
+        self._interface_op = None  # InterfaceOp on the model's device
 
     def load_reference_state_dict(self, sd):
         """Reference-keyed LitGINI state dict. The head loads into this nn.Module; the GeoT
@@ -477,13 +478,18 @@ class LitGINI(nn.Module):
         test_labels are copied to the host only for the first ``keep_maps`` complexes (None: all; the
         reference keeps 55 of an epoch); the other dicts hold None there. The host reads the device
         once for the labels' validation, once per metrics table and once for all top_hits."""
-        import os
         if not (len(pairs) == len(examples_list) == len(filepaths)):
             raise ValueError("test_batch: one examples tensor and one file path per complex")
         logits_list, _, _ = self._forward_batch(gb, pairs)
-        rank, auc_op = self._ranker(), self._auc()
         shapes = [(int(lg.shape[2]), int(lg.shape[3])) for lg in logits_list]
-        labels = labels_from_examples_batch([ex.to(rank.device) for ex in examples_list], shapes)
+        labels = labels_from_examples_batch([ex.to(self._ranker().device) for ex in examples_list], shapes)
+        return self._test_batch_dicts(logits_list, shapes, labels, filepaths, keep_maps)
+
+    def _test_batch_dicts(self, logits_list, shapes, labels, filepaths, keep_maps):
+        """test_batch's tail: the batched ranking and AUC calls over the logits and their uint8 label
+        maps, and one test_step dict per complex."""
+        import os
+        rank, auc_op = self._ranker(), self._auc()
         ranks = rank.batch([lg.contiguous() for lg in logits_list], labels_list=labels,
                            threshold=self.pos_prob_threshold)
         aucs = auc_op.batch([r.probs for r in ranks], labels)   # the maps the ranking judged
@@ -508,15 +514,43 @@ class LitGINI(nn.Module):
             outs.append(out)
         return outs
 
+    def _interface(self):
+        dev = self.engine.device
+        if self._interface_op is None or self._interface_op.device != dev:
+            self._interface_op = InterfaceOp(dev)
+        return self._interface_op
+
+    def test_batch_structures(self, gb: GraphBatch, pairs, structures, filepaths, keep_maps=None, cutoff=6.0):
+        """``test_batch`` from structures instead of example lists: structures[i] = ((xyz0, res_off0),
+        (xyz1, res_off1)), complex i's heavy atoms per chain as ``ranking.interface_atoms`` groups them
+        (numpy arrays or tensors on the model's GPU). The label maps come from ``ranking.InterfaceOp``
+        (residues interact iff two of their heavy atoms lie within ``cutoff``, 6 A in DIPS); everything
+        after them is test_batch's, and so are the dicts. A chain whose residue count differs from its
+        graph's node count raises ValueError before any launch."""
+        if not (len(pairs) == len(structures) == len(filepaths)):
+            raise ValueError("test_batch_structures: one structure and one file path per complex")
+        for i, ((a, b), (c0, c1)) in enumerate(zip(pairs, structures)):
+            want = (gb.nodes_per_graph[a], gb.nodes_per_graph[b])
+            got = (int(c0[1].shape[0]) - 1, int(c1[1].shape[0]) - 1)
+            if got != want:
+                raise ValueError(f"test_batch_structures: complex {i}'s chains have {got} residues, "
+                                 f"its graphs {want} nodes")
+        logits_list, _, _ = self._forward_batch(gb, pairs)
+        shapes = [(int(lg.shape[2]), int(lg.shape[3])) for lg in logits_list]
+        labels = self._interface().labels([s[0] for s in structures], [s[1] for s in structures], cutoff=cutoff)
+        return self._test_batch_dicts(logits_list, shapes, labels, filepaths, keep_maps)
+
     def test_sharded(self, complexes, examples_list, filepaths, micro_batch=8, k=20, seed=0, group=None,
-                     device=None):
+                     device=None, structures=None, cutoff=6.0):
         """test_step over a test set sharded across a process group (``distributed.test_sharded``):
         every rank ranks and scores its shard on the device, ONE all-gather moves a KB-sized record
         per complex, and every rank returns every complex's test_batch dict (maps None; ``top_ids`` /
-        ``top_scores`` added), ready for ``test_epoch_end(outs)`` without a group."""
+        ``top_scores`` added), ready for ``test_epoch_end(outs)`` without a group. The labels come from
+        ``examples_list`` or, with ``examples_list=None``, from ``structures`` (as
+        ``test_batch_structures`` takes them; ``cutoff`` in A): exactly one of the two."""
         from .distributed import test_sharded
         return test_sharded(self, complexes, examples_list, filepaths, micro_batch=micro_batch, k=k, seed=seed,
-                            group=group, device=device)
+                            group=group, device=device, structures=structures, cutoff=cutoff)
 
     def _examples(self):
         dev = self.engine.device

@@ -23,7 +23,9 @@ with one launch sequence (``di_contact_rank_batch`` / ``di_contact_auc_batch``) 
 the bits of the single call; ``labels_from_examples_batch`` validates a batch's labels with one host
 read. ``ExamplesOp`` reads the example lists on the device (csrc/contact_examples.hip): complete lists
 as label maps, sampled lists as ``LitGINI.validation_step``'s pooled logits and labels;
-``pooled_topk_metrics`` is that step's top-k arithmetic.
+``pooled_topk_metrics`` is that step's top-k arithmetic. ``InterfaceOp`` builds the label maps from the
+two chains' heavy-atom coordinates instead (csrc/contact_interface.hip; ``interface_atoms`` groups a
+chain's atoms for it), so a prediction can be scored from a structure, without example lists.
 
 Across ranks: ``ContactRankOp.batch(out=...)`` / ``ContactAucOp.batch(out=...)`` write a complex's
 ranked contacts and metrics into caller memory -- ``RecordSlot``, the views of one wire record
@@ -697,6 +699,148 @@ class ExamplesOp:
         return out
 
 
+def interface_atoms(xyz, residue_index, element=None):
+    """One chain's atoms as ``InterfaceOp`` takes them: ``(xyz float32 [A, 3], res_off int32 [L + 1])``,
+    the heavy atoms grouped by residue with CSR offsets. Host, numpy. xyz: [N, 3] coordinates;
+    residue_index: one entry per atom ([N] of any dtype, or [N, m] rows such as (number, insertion
+    code)) -- atoms of one residue follow each other, and residues are numbered in order of first
+    appearance; element (optional): one symbol per atom, atoms whose symbol is 'H' (any case, spaces
+    ignored) are dropped. ValueError for arrays of other shapes, a chain left without atoms, or a
+    residue index that reappears after another one."""
+    import numpy as np
+    xyz = np.asarray(xyz)
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError("interface atoms: xyz is [N, 3]")
+    res = np.asarray(residue_index)
+    if res.ndim == 1:
+        res = res[:, None]
+    if res.ndim != 2 or res.shape[0] != xyz.shape[0]:
+        raise ValueError("interface atoms: one residue index per atom")
+    if element is not None:
+        el = np.char.upper(np.char.strip(np.asarray(element, dtype=str)))
+        if el.shape != (xyz.shape[0],):
+            raise ValueError("interface atoms: one element symbol per atom")
+        xyz, res = xyz[el != "H"], res[el != "H"]
+    if xyz.shape[0] < 1:
+        raise ValueError("interface atoms: the chain has no heavy atoms")
+    starts = np.concatenate(([0], np.flatnonzero((res[1:] != res[:-1]).any(axis=1)) + 1))
+    if len(np.unique(res[starts], axis=0)) != len(starts):
+        raise ValueError("interface atoms: a residue index reappears after another residue "
+                         "(the atoms of one residue follow each other)")
+    res_off = np.concatenate((starts, [xyz.shape[0]])).astype(np.int32)
+    return np.ascontiguousarray(xyz, dtype=np.float32), res_off
+
+
+_IF_OFFSETS = "interface: residue offsets do not start at 0, decrease, or do not end at the atom count"
+_IF_EMPTY = "interface: a residue without atoms"
+_IF_NONFINITE = "interface: a NaN or Inf coordinate"
+
+
+class InterfaceOp:
+    """The label maps of bound complexes from their chains' heavy-atom coordinates on HIP
+    (csrc/contact_interface.hip, ``di_interface_labels_batch``): residue i of chain 0 and residue j of
+    chain 1 interact iff some atom of i lies within ``cutoff`` (<=) of some atom of j -- the definition
+    behind DIPS' pos_idx (deepinteract_utils.py:612: non-hydrogen atoms, 6 A), from which the reference's
+    ``build_examples_tensor`` makes its example lists. One memset and two launches per DI_BATCH_MAX
+    complexes, one host read (the stats) per call. No CPU fallback."""
+
+    def __init__(self, device="cuda"):
+        self.device = gpu_device(device)
+        self.lib = _lib.load()
+        self.num_pos = []
+
+    def labels(self, chains0, chains1, cutoff=6.0):
+        """chains0[i] / chains1[i]: complex i's ``(xyz [A, 3], res_off [L + 1])`` per chain
+        (``interface_atoms``), numpy arrays or tensors on the op's GPU -> one uint8 [l1 * l2] map per
+        complex, views of one packed buffer that each start 16-B aligned, as ``ExamplesOp.labels``
+        returns them. The pair test is fp32 and fixed to the bit: d2 = (dx * dx + dy * dy) + dz * dz
+        <= (float)(cutoff * cutoff). All host arrays of a call go to the device in ONE pinned packed
+        copy on the current stream; device tensors are read where they are (converted to contiguous
+        fp32 / int32 if they are not). ``num_pos`` keeps the call's positives per complex (ints).
+        Raises ValueError for arrays of other shapes or a cutoff that is not finite and positive, before
+        any launch; then, for the first complex that has a fault, malformed offsets, a residue without
+        atoms, a NaN or Inf coordinate, in this order."""
+        import math
+
+        import numpy as np
+        count = len(chains0)
+        if count < 1 or len(chains1) != count:
+            raise ValueError("interface: one non-empty list of chains per side, of one length")
+        cutoff = float(cutoff)
+        as_f32 = ctypes.c_float(cutoff).value       # what the kernels get
+        if not math.isfinite(as_f32) or as_f32 <= 0:
+            raise ValueError(f"interface: cutoff = {cutoff}: finite and positive")
+        host, words = [], 0       # (array, word offset in the packed copy)
+        chains = []               # per complex and side: [xyz, res_off], a tensor or an index into host
+
+        def take(a, dtype, tdtype):
+            nonlocal words
+            if isinstance(a, torch.Tensor):
+                check_on(self.device, "InterfaceOp", a)
+                return a.to(tdtype).contiguous()
+            a = np.ascontiguousarray(a, dtype=dtype)
+            host.append((a, words))
+            words += a.size
+            return len(host) - 1
+
+        shapes = []
+        for pair in zip(chains0, chains1):
+            sizes = []
+            for xyz, off in pair:
+                if len(xyz.shape) != 2 or xyz.shape[1] != 3 or len(off.shape) != 1:
+                    raise ValueError("interface: a chain is (xyz [A, 3], res_off [L + 1])")
+                a, l = int(xyz.shape[0]), int(off.shape[0]) - 1
+                if a < 1 or l < 1:
+                    raise ValueError("interface: a chain has at least one residue and one atom")
+                chains.append([take(xyz, np.float32, torch.float32), take(off, np.int32, torch.int32)])
+                sizes.append((l, a))
+            shapes.append(sizes)
+        if host:
+            pinned = torch.empty(words, dtype=torch.int32, pin_memory=True)
+            flat = pinned.numpy()
+            for a, at in host:
+                flat[at:at + a.size] = a.reshape(-1).view(np.int32)
+            packed = pinned.to(self.device, non_blocking=True)
+            for c in chains:
+                for s, tdtype in ((0, torch.float32), (1, torch.int32)):
+                    if not isinstance(c[s], torch.Tensor):
+                        a, at = host[c[s]]
+                        c[s] = packed[at:at + a.size].view(tdtype)
+        off_map, at = [], 0
+        for (l1, _), (l2, _) in shapes:
+            off_map.append(at)
+            at += (l1 * l2 + 15) // 16 * 16
+        maps = torch.empty(at, dtype=torch.uint8, device=self.device)
+        outs = [maps[o:o + s[0][0] * s[1][0]] for o, s in zip(off_map, shapes)]
+        items = (_lib.DiInterfaceItem * count)()
+        for i, (it, out, ((l1, a0), (l2, a1))) in enumerate(zip(items, outs, shapes)):
+            (x0, o0), (x1, o1) = chains[2 * i], chains[2 * i + 1]
+            it.xyz0, it.res_off0, it.xyz1, it.res_off1 = (t.data_ptr() for t in (x0, o0, x1, o1))
+            it.labels, it.l1, it.l2, it.a0, it.a1 = out.data_ptr(), l1, l2, a0, a1
+        stats = []
+        for lo in range(0, count, _lib.DI_BATCH_MAX):
+            m = min(_lib.DI_BATCH_MAX, count - lo)
+            part = (_lib.DiInterfaceItem * m).from_buffer(items, lo * ctypes.sizeof(_lib.DiInterfaceItem))
+            nb = self.lib.di_interface_work_bytes(part, m)
+            if nb < 0:
+                raise ValueError(f"interface of a batch of {m}: code {nb} (l1 * l2 < 2^29, a chain's atoms < 2^24)")
+            # its own workspace per launch: the stats at its front are read after the last one
+            work = torch.empty(nb // 8, dtype=torch.int64, device=self.device)
+            part_dev = _table_to_device(part, self.device)
+            _lib.check(self.lib.di_interface_labels_batch(part, _ptr(part_dev), m, ctypes.c_float(cutoff), _ptr(work),
+                                                          _stream()), "di_interface_labels_batch")
+            stats.append(work[:2 * m])
+        rows =(stats[0] if len(stats) == 1 else torch.cat(stats)).cpu().view(count, 2).tolist()
+        for _, word in rows:
+            f = word & 0xffffffff
+            for bit, text in ((_lib.DI_IF_OFFSETS, _IF_OFFSETS), (_lib.DI_IF_EMPTY, _IF_EMPTY),
+                              (_lib.DI_IF_NONFINITE, _IF_NONFINITE)):
+                if f & bit:
+                    raise ValueError(text)
+        self.num_pos = [int(n) for n, _ in rows]
+        return outs
+
+
 def confusion_metrics(tp, fp, fn, tn) -> dict:
     """test_acc / test_prec / test_recall / test_f1 of LitGINI.test_step from the confusion counts at
     pos_prob_threshold, as torchmetrics' multiclass (num_classes=2, average=None) metrics define them
@@ -836,5 +980,5 @@ def pooled_topk_metrics(hits, num_pos, l: int, n: int) -> dict:
 
 
 __all__ = ["ContactRankOp", "ContactRanking", "ContactRankingBatch", "ContactAucOp", "ContactAuc",
-           "ExamplesOp", "GatheredRanking", "RecordSlot", "record_k", "confusion_metrics", "labels_from_examples", "labels_from_examples_batch",
+           "ExamplesOp", "InterfaceOp", "interface_atoms", "GatheredRanking", "RecordSlot", "record_k", "confusion_metrics", "labels_from_examples", "labels_from_examples_batch",
            "labels_from_examples_batch_torch", "pooled_topk_metrics", "topk_metrics"]

@@ -40,6 +40,8 @@
  *   di_contact_rank_batch / di_contact_auc_batch  both over many complexes in one launch sequence
  *   di_examples_labels_batch / di_examples_gather_batch  a batch's example lists as label maps, or
  *                     as validation_step's pooled logits and labels  deepinteract_modules.py:1915-1982
+ *   di_interface_labels_batch  a batch's label maps from the chains' heavy-atom coordinates
+ *                     (what build_examples_tensor reads from pos_idx)  deepinteract_utils.py:567-582, 612
  *
  * Module-at-a-time entry points (deepinteract_amd/layers.py; same math as the fused kernels):
  *   di_conformation   ConformationModule.forward                      deepinteract_modules.py:373-455
@@ -786,6 +788,56 @@ int di_examples_gather_batch(int32_t dtype, int32_t idx_dtype, const di_examples
                              const di_examples_item* items_dev, int32_t count, int32_t* flags, void* stream);
 int di_examples_gather_batch_check(int32_t dtype, int32_t idx_dtype, const di_examples_item* items,
                                    const di_examples_item* items_dev, int32_t count, const int32_t* flags);
+
+/* ---- interface label maps from atom coordinates (an addition to ABI 8) -----------------------
+ * The label map of each of `count` bound complexes from its two chains' heavy atoms, by the
+ * definition behind DIPS' pos_idx (deepinteract_utils.py:612: neighbor_def='non_heavy_res',
+ * cutoff=6): labels[i * l2 + j] = 1 iff some atom of residue i of chain 0 lies within `cutoff` (<=)
+ * of some atom of residue j of chain 1, uint8 [l1 * l2], the map di_contact_rank / di_contact_auc
+ * take and di_examples_labels_batch writes. One memset (the stats) and TWO launches, whatever count
+ * is. Tables and grid as for di_contact_rank_batch (host items validated and used for grid sizes;
+ * items_dev the caller's device copy).
+ *   per chain: xyz [a, 3] fp32 heavy-atom coordinates grouped by residue; res_off [l + 1] int32 CSR
+ *   offsets into xyz (res_off[0] = 0, non-decreasing, res_off[l] = a).
+ * The pair test, to the bit: dx = x0 - x1 (likewise dy, dz), d2 = (dx * dx + dy * dy) + dz * dz,
+ * every operation rounded to fp32 and none contracted; contact iff d2 <= c2, c2 =
+ * (float)((double)cutoff * (double)cutoff); a comparison against NaN is false. Residue pairs whose
+ * bounding spheres (computed centre, largest computed distance from it) are provably farther apart
+ * than cutoff are not examined; the margin argument is in csrc/contact_interface.hip. Every byte of
+ * every map is written exactly once (no memset of the maps, no atomics on them).
+ * work: di_interface_work_bytes bytes, 16-B aligned. Its first `count` 16-byte records are the
+ * di_interface_stats of the complexes (cleared in-stream by the call): num_pos = the map's positives,
+ * flags = DI_IF_OFFSETS (res_off[0] != 0, a decreasing pair, or res_off[l] != a; every residue's range
+ * is clamped into [0, a] before use, so nothing outside xyz is read), DI_IF_EMPTY (a residue with no
+ * atoms), DI_IF_NONFINITE (a NaN or Inf coordinate). Both are functions of the input alone (integer
+ * adds, ORs of constants). A flagged complex's map is unspecified, but every write stays inside it;
+ * its neighbours are not affected. The helper fills work_off (the complex's spheres, after the
+ * stats), and the call refuses other values.
+ * Asynchronous, no allocation, every refusal before any launch; the _check form does the same
+ * validation on the host, without a launch. DI_EINVAL: count < 1, a NULL table / work / item pointer,
+ * l1, l2, a0 or a1 < 1, cutoff not finite or not positive, work not 16-B aligned, xyz or res_off not
+ * 4-B aligned, a work_off the helper did not fill. DI_ERANGE: count > DI_BATCH_MAX,
+ * l1 * l2 >= 2^29, a chain of 2^24 atoms or more. */
+enum { DI_IF_OFFSETS = 1, DI_IF_EMPTY = 2, DI_IF_NONFINITE = 4 };
+typedef struct {
+  const float* xyz0;
+  const int32_t* res_off0;
+  const float* xyz1;
+  const int32_t* res_off1;
+  uint8_t* labels;
+  int32_t l1, l2, a0, a1;
+  int64_t work_off;
+} di_interface_item;
+typedef struct {
+  int64_t num_pos;
+  int32_t flags;
+  int32_t pad;
+} di_interface_stats;
+int64_t di_interface_work_bytes(di_interface_item* items, int32_t count);
+int di_interface_labels_batch(const di_interface_item* items, const di_interface_item* items_dev, int32_t count,
+                              float cutoff, void* work, void* stream);
+int di_interface_labels_batch_check(const di_interface_item* items, const di_interface_item* items_dev,
+                                    int32_t count, float cutoff, const void* work);
 
 /* ---- graph builder ----------------------------------------------------------------------- */
 /* Cα kNN per chain: idx_out [Nt,k] chain-local neighbour ids (ascending squared distance,
