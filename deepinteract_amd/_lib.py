@@ -103,6 +103,23 @@ class DiInterfaceStats(ctypes.Structure):
     _fields_ = [("num_pos", ctypes.c_int64), ("flags", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+DI_ENV_OFFSETS, DI_ENV_EMPTY, DI_ENV_NONFINITE, DI_ENV_BACKBONE = 1, 2, 4, 8
+DI_ROLE_OTHER, DI_ROLE_N, DI_ROLE_CA, DI_ROLE_C, DI_ROLE_O, DI_ROLE_CB = range(6)
+DI_ENV_C2 = 55.262043       # (float)(8 ln 1000): exp(-d2 / 8) > 1e-3
+
+
+class DiEnvItem(ctypes.Structure):
+    _fields_ = [("xyz", ctypes.c_void_p), ("res_off", ctypes.c_void_p), ("role", ctypes.c_void_p),
+                ("aa", ctypes.c_void_p), ("resname", ctypes.c_void_p), ("dips", ctypes.c_void_p),
+                ("amide_norm", ctypes.c_void_p), ("backbone", ctypes.c_void_p), ("cn_raw", ctypes.c_void_p),
+                ("l", ctypes.c_int32), ("a", ctypes.c_int32), ("work_off", ctypes.c_int64)]
+
+
+class DiEnvStats(ctypes.Structure):
+    _fields_ = [("flags", ctypes.c_int32), ("cn_max", ctypes.c_int32), ("cn_min_gap", ctypes.c_int32),
+                ("pad", ctypes.c_int32)]
+
+
 class DiHeadConvArgs(ctypes.Structure):
     _fields_ = [("x", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("in_scale", ctypes.c_void_p),
                 ("in_shift", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("y", ctypes.c_void_p),
@@ -229,6 +246,9 @@ _SIGS = {
     "di_interface_work_bytes": ([_P, _I], ctypes.c_int64),
     "di_interface_labels_batch": ([_P, _P, _I, ctypes.c_float, _P, _P], ctypes.c_int),
     "di_interface_labels_batch_check": ([_P, _P, _I, ctypes.c_float, _P], ctypes.c_int),
+    "di_residue_env_work_bytes": ([_P, _I], ctypes.c_int64),
+    "di_residue_env_batch": ([_P, _P, _I, ctypes.c_float, _P, _P], ctypes.c_int),
+    "di_residue_env_batch_check": ([_P, _P, _I, ctypes.c_float, _P], ctypes.c_int),
     "di_knn_topk": ([_I, _P, _P, _I, _I, _P, _P, _P], ctypes.c_int),
     "di_geo_feats": ([ctypes.POINTER(DiGeoArgs), _P], ctypes.c_int),
     "di_build_nbr_ids": ([_I, _P, _P, _P, ctypes.c_uint64, _P, _P], ctypes.c_int),

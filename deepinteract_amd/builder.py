@@ -126,6 +126,16 @@ def build_graph_batch(chains, k=KNN, nb=GEO_NBRHD_SIZE, seed=0, device="cuda", r
     dips = d_all[nt * 15:nt * 121].view(nt, 106)
     d_meta = d_all[m0:words].view(torch.int32)
     off = d_meta[:G + 1]
+    seeds = d_meta[n_off:] if nbr_seeds is not None else None
+    return _build_on_device(lib, bb, am, dips, off, seeds, sizes, k, seed, node_count_limit, return_aux, (d_all,))
+
+
+def _build_on_device(lib, bb, am, dips, off, seeds, sizes, k, seed, node_count_limit, return_aux, keep):
+    """The builder's launches over a batch already on the device: bb [nt, 4, 3], am [nt, 3], dips
+    [nt, 106] fp32, off [G + 1] int32 node offsets, seeds [G] uint64 as int32 words (or None: the
+    counter-based RNG keyed by `seed`). `keep`: what the in-flight launches read."""
+    device = bb.device
+    nt, G = int(sum(sizes)), len(sizes)
     ca = bb[:, 1, :].contiguous()
     idx, d2 = _knn(ca, sizes, off, k)
     node_f = torch.empty(nt, 113, dtype=torch.float32, device=device)
@@ -141,8 +151,7 @@ def build_graph_batch(chains, k=KNN, nb=GEO_NBRHD_SIZE, seed=0, device="cuda", r
     _lib.check(lib.di_knn_graph(G, _p(off), k, _p(idx), nt, _p(src), _p(dst), _p(in_ptr), _p(node_pos), _stream()),
                "di_knn_graph")
     nbr = torch.empty(nt * k, 4, dtype=torch.int32, device=device)
-    if nbr_seeds is not None:
-        seeds = d_meta[n_off:]
+    if seeds is not None:
         _lib.check(lib.di_build_nbr_ids_torch(G, _p(off), k, _p(seeds), nt, _p(src), _p(dst), _p(nbr), _stream()),
                    "di_build_nbr_ids_torch")
     else:
@@ -152,7 +161,50 @@ def build_graph_batch(chains, k=KNN, nb=GEO_NBRHD_SIZE, seed=0, device="cuda", r
     # for every edge, so the batch carries DI_GRAPH_GEO_REF by construction (no device check)
     gb = GraphBatch(src, dst, nbr, node_f, edge_f, sizes, [n * k for n in sizes], node_count_limit=node_count_limit,
                     in_ptr=in_ptr, node_pos=node_pos, _trusted_geo_ref=True)
-    gb._keep = (d_all,)  # inputs referenced by in-flight launches
+    gb._keep = keep  # inputs referenced by in-flight launches
     if return_aux:
         return gb, {"knn_idx": idx, "knn_d2": d2}
     return gb
+
+
+def build_graph_batch_structures(chains, extern=None, k=KNN, nb=GEO_NBRHD_SIZE, seed=0, device="cuda",
+                                 return_aux=False, node_count_limit=NODE_COUNT_LIMIT, nbr_seeds=None):
+    """``build_graph_batch`` from structures: chains[i] is ``structure.residue_atoms``' tuple (xyz,
+    res_off, role, aa, resname_idx), numpy arrays or tensors on the GPU; extern[i] optionally supplies
+    the 43 DIPS-Plus columns that need external programs (``structure.EXTERN_COLUMNS``; zeros otherwise).
+    ``structure.ResidueEnvOp`` computes backbone, amide normals and the structure-derived columns on the
+    device, and the builder's launches read them there: the features make no host round trip. Limits,
+    errors and the other arguments are ``build_graph_batch``'s; the op's ValueErrors pass through.
+    return_aux adds the op's result (``"env"``) to the aux dict."""
+    if nb != 2:
+        raise NotImplementedError("geo_nbrhd_size=2 (the reference's setting, lit_model_predict.py:156)")
+    from .engine import gpu_device
+    from .structure import ResidueEnvOp
+    sizes = [int(c[3].shape[0]) for c in chains]
+    for n in sizes:
+        if n > node_count_limit:
+            raise IndexError(f"chain of {n} residues exceeds NODE_COUNT_LIMIT={node_count_limit}")
+        if n > BUILDER_MAX_NODES:
+            raise NotImplementedError(f"chain of {n} residues: the on-device kNN handles chains of at most "
+                                      f"{BUILDER_MAX_NODES} residues (di_knn_topk)")
+    if nbr_seeds is not None and len(nbr_seeds) != len(sizes):
+        raise ValueError(f"{len(nbr_seeds)} neighbour seeds for {len(sizes)} chains")
+    if sizes and min(sizes) < k:
+        raise ValueError(f"a chain has fewer than k={k} residues")
+    device = gpu_device(device)
+    env = ResidueEnvOp(device).features(chains, extern=extern)
+    G = len(sizes)
+    n_off = (G + 2) // 2 * 2  # int32 offsets padded to 8 bytes, then the uint64 seeds
+    meta = torch.zeros(n_off + 2 * (G if nbr_seeds is not None else 0), dtype=torch.int32, pin_memory=True)
+    hm = meta.numpy()
+    hm[1:G + 1] = np.cumsum(sizes)
+    if nbr_seeds is not None:
+        hm[n_off:].view(np.uint64)[:] = np.asarray(nbr_seeds, dtype=np.uint64)
+    d_meta = meta.to(device, non_blocking=True)
+    seeds = d_meta[n_off:] if nbr_seeds is not None else None
+    p = env.packed
+    out = _build_on_device(_lib.load(), p["backbone"], p["amide_norm"], p["dips"], d_meta[:G + 1], seeds, sizes, k,
+                           seed, node_count_limit, return_aux, (env, d_meta))
+    if return_aux:
+        out[1]["env"] = env
+    return out

@@ -49,6 +49,7 @@
 // reads from the device table, and returns at once when x is past that complex's own block count.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "atom_pairs.h"   // if_dist2, the sphere record, IF_MARGIN, IF_MAX_ATOMS
 #include "common.h"
 #include "../../include/deepinteract_amd.h"
 
@@ -61,21 +62,6 @@ constexpr int IF_ROWS = 4;                       // i rows of a tile per wave
 constexpr int IF_TI = IF_WAVES * IF_ROWS;        // i residues of a tile
 constexpr int IF_CAP = 2048;                     // j-side atoms staged in LDS at a time (24 KiB)
 constexpr int64_t IF_MAX_PAIRS = (int64_t)1 << 29;
-constexpr int32_t IF_MAX_ATOMS = 1 << 24;
-constexpr float IF_MARGIN = 1.0f + 0x1p-18f;     // see the soundness argument above
-
-// (dx * dx + dy * dy) + dz * dz in fp32, every operation rounded on its own
-__device__ __forceinline__ float if_dist2(float x0, float y0, float z0, float x1, float y1, float z1) {
-#pragma clang fp contract(off)
-  const float dx = x0 - x1, dy = y0 - y1, dz = z0 - z1;
-  const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-  const float xy = xx + yy;
-  return xy + zz;
-}
-
-__device__ __forceinline__ int if_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-__device__ __forceinline__ bool if_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }   // false for NaN
 
 __global__ __launch_bounds__(IF_THREADS) void k_interface_spheres(const di_interface_item* __restrict__ items,
                                                                   char* __restrict__ work) {
@@ -152,9 +138,7 @@ __global__ __launch_bounds__(IF_THREADS) void k_interface_labels(const di_interf
     const int i = i_base + s;
     if (i < l1 && have_j) {
       const float4 si = sph0[i];
-      const float dist = sqrtf(if_dist2(si.x, si.y, si.z, sj.x, sj.y, sj.z));
-      const float reach = ((cutoff + si.w) + sj.w) * IF_MARGIN;
-      if (!(dist > reach)) live |= 1u << s;         // NaN: not provably apart
+      if (if_may_touch(si, sj, cutoff)) live |= 1u << s;   // NaN: not provably apart
     }
   }
   unsigned hit = 0;

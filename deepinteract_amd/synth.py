@@ -115,8 +115,12 @@ def synthetic_complex(c: int, n1: int, n2: int, homodimer: bool = False):
 
 
 def read_pdb_chain(path: str, seed: int = 0):
-    """Backbone + amide normals from a PDB file (ATOM records, fixed columns). DIPS-Plus
-    columns are not derivable offline (PSAIA / HH-suite), so they are seeded synthetic."""
+    """Backbone + amide normals from a PDB file (ATOM records, fixed columns), with SEEDED SYNTHETIC
+    DIPS-Plus columns past the residue one-hot (the golden vectors depend on these values). Of the 106
+    columns, 0:20 (residue one-hot), 36:78 (HSAAC) and 78 (coordination number), and the amide normals,
+    are derivable from the atoms: ``structure.read_pdb`` / ``structure.residue_atoms`` /
+    ``structure.ResidueEnvOp`` compute them on the device, ``builder.build_graph_batch_structures`` builds
+    the batch from them. Only 20:36 (DSSP, MSMS, PSAIA) and 79:106 (HH-suite) need external programs."""
     residues = {}
     order = []
     with open(path) as fh:

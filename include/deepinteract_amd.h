@@ -42,6 +42,8 @@
  *                     as validation_step's pooled logits and labels  deepinteract_modules.py:1915-1982
  *   di_interface_labels_batch  a batch's label maps from the chains' heavy-atom coordinates
  *                     (what build_examples_tensor reads from pos_idx)  deepinteract_utils.py:567-582, 612
+ *   di_residue_env_batch  a batch's structure-derived DIPS-Plus columns (residue one-hot, HSAAC, CN)
+ *                     and amide normals from the chains' atoms        dips_plus_utils.py:84-161, 356-374
  *
  * Module-at-a-time entry points (deepinteract_amd/layers.py; same math as the fused kernels):
  *   di_conformation   ConformationModule.forward                      deepinteract_modules.py:373-455
@@ -838,6 +840,76 @@ int di_interface_labels_batch(const di_interface_item* items, const di_interface
                               float cutoff, void* work, void* stream);
 int di_interface_labels_batch_check(const di_interface_item* items, const di_interface_item* items_dev,
                                     int32_t count, float cutoff, const void* work);
+
+/* ---- residue environment features from atoms (an addition to ABI 8) --------------------------
+ * The DIPS-Plus node-feature columns that are functions of a chain's atoms alone, and its amide
+ * normals and backbone rows, for each of `count` chains of a ragged batch: one memset (the stats)
+ * and THREE launches, whatever count is. Tables and grid as for di_interface_labels_batch.
+ *   per chain: xyz [a, 3] fp32 coordinates of ALL atoms grouped by residue (hydrogens too where the
+ *   file has them); res_off [l + 1] int32 CSR offsets; role [a] uint8 per atom (DI_ROLE_*); aa [l]
+ *   uint8, the index into "ACDEFGHIKLMNPQRSTVWY-" ('-' = 20: not one of the standard twenty);
+ *   resname [l] uint8, the one-hot column 0..19 (TRP PHE LYS PRO ASP ALA ARG CYS VAL THR GLY SER
+ *   HIS LEU GLU TYR ILE ASN MET GLN; an unknown residue goes to the last).
+ * Every residue holds exactly one N, CA, C and O and at most one CB (DI_ENV_BACKBONE otherwise).
+ *   nb(i, j): some atom of i and some atom of j have d2 < c2 (STRICT; d2 as in
+ *     di_interface_labels_batch, fp32, every operation rounded, none contracted); nb(i, i) always.
+ *     The default c2 is DI_ENV_C2 = (float)(8 ln 1000): exp(-d2 / 8) > 1e-3.
+ *   CN_i = #{j : nb(i, j)}, self included -> cn_raw [l] int32.
+ *   u_i = the mean of the unit vectors from CA to the atoms whose role is not N, CA, C or O; without
+ *     such atoms 1/2 [(CA - C) / |CA - C| + (CA - N) / |CA - N|]. fp32; only signs of dot products
+ *     with it are used.
+ *   j != i with nb(i, j) is UP iff dot(u_i, CA_j - CA_i) > 0, else DOWN (a zero or NaN dot: down);
+ *     i itself counts as DOWN. UN_i = #up, DN_i = CN_i - UN_i.
+ *   dips [l, 106] fp32, row stride 106; the call writes ONLY these columns and leaves the others:
+ *     0:20   the one-hot of resname
+ *     36:57  UC[t] = ([t == aa_i] + #{up j: aa_j = t}) / (1 + UN_i), t = 0..20
+ *     57:78  DC[t] = ([t == aa_i] + #{down j, i included: aa_j = t}) / (1 + DN_i)
+ *     78     (CN_i - min) / (max - min) over the chain, 0 when max == min
+ *     every value the fp32 quotient of two integers.
+ *   amide_norm [l, 3]: cross(CA - CB, CB - N), every operation rounded to fp32 and none contracted;
+ *     zeros without a CB. backbone [l, 4, 3]: the N, CA, C, O coordinates.
+ * All counts are integers accumulated with integer adds, so every output is a function of the input
+ * alone, whatever the schedule. Residue pairs whose bounding spheres are provably farther apart than
+ * sqrt(c2) are not examined (csrc/atom_pairs.h, the argument in csrc/contact_interface.hip).
+ * work: di_residue_env_work_bytes bytes, 16-B aligned. Its first `count` 16-byte records are the
+ * di_env_stats of the chains (cleared in-stream by the call): flags = DI_ENV_OFFSETS / DI_ENV_EMPTY
+ * / DI_ENV_NONFINITE as DI_IF_* (ranges are clamped into [0, a] before use: nothing outside the
+ * chain's arrays is read), DI_ENV_BACKBONE (a role > 5, an aa > 20, a resname > 19, or a residue
+ * without exactly one N, CA, C, O and at most one CB); cn_max = max CN; cn_min_gap = l - min CN.
+ * A flagged chain's outputs are unspecified but every write stays inside its own buffers; its
+ * neighbours in the batch are not affected. The helper fills work_off, and the call refuses others.
+ * Asynchronous, no allocation, every refusal before any launch; the _check form validates on the
+ * host without a launch. DI_EINVAL: count < 1, a NULL table / work / item pointer, l or a < 1, c2 not
+ * finite or not positive, work not 16-B aligned, xyz / res_off / dips / amide_norm / backbone /
+ * cn_raw not 4-B aligned, a work_off the helper did not fill. DI_ERANGE: count > DI_BATCH_MAX, a
+ * chain of 2^24 atoms or residues or more. */
+#define DI_ENV_C2 55.262043f
+enum { DI_ROLE_OTHER = 0, DI_ROLE_N = 1, DI_ROLE_CA = 2, DI_ROLE_C = 3, DI_ROLE_O = 4, DI_ROLE_CB = 5 };
+enum { DI_ENV_OFFSETS = 1, DI_ENV_EMPTY = 2, DI_ENV_NONFINITE = 4, DI_ENV_BACKBONE = 8 };
+typedef struct {
+  const float* xyz;
+  const int32_t* res_off;
+  const uint8_t* role;
+  const uint8_t* aa;
+  const uint8_t* resname;
+  float* dips;
+  float* amide_norm;
+  float* backbone;
+  int32_t* cn_raw;
+  int32_t l, a;
+  int64_t work_off;
+} di_env_item;
+typedef struct {
+  int32_t flags;
+  int32_t cn_max;
+  int32_t cn_min_gap;
+  int32_t pad;
+} di_env_stats;
+int64_t di_residue_env_work_bytes(di_env_item* items, int32_t count);
+int di_residue_env_batch(const di_env_item* items, const di_env_item* items_dev, int32_t count, float c2,
+                         void* work, void* stream);
+int di_residue_env_batch_check(const di_env_item* items, const di_env_item* items_dev, int32_t count, float c2,
+                               const void* work);
 
 /* ---- graph builder ----------------------------------------------------------------------- */
 /* Cα kNN per chain: idx_out [Nt,k] chain-local neighbour ids (ascending squared distance,
